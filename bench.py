@@ -16,7 +16,12 @@ loop on the device, and the final warp of all 8192 source points.  The point clo
 HBM before the timed region.  Pairs shard over ranks (weak scaling: the same number of pairs per
 GPU); the only collective is the final all-reduce of the aggregate (RCCL).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement / DESIGN.md).
+A plain run sets up, warms up, times the K steps and prints the headline (pairs/s, ms_per_step).  `--full` adds what the
+headline does not need: the accuracy of the last step's pairs, the other arithmetic configuration, rooflines, the surface-pair
+accuracy, the batch-1 latency and the CPU baseline (each still switched off by its --no-* option).  `--dump-outputs DIR` writes
+what the timed path computed in its last step (see dump_outputs) before the line is printed.
+
+Prints ONE JSON line on rank 0 (its figures: DESIGN.md section 6).
 """
 import argparse
 import json
@@ -419,6 +424,34 @@ def cpu_baseline(cfg, pairs):
             "ports": rep, "oversubscribed": over, "whole_box": whole}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6          # --dump-outputs: all files together
+
+
+def dump_selection(n_pairs, pair_bytes, other_bytes, limit=DUMP_LIMIT_BYTES):
+    """Indices (sorted) of the pairs of a step whose warped clouds --dump-outputs writes: all of them when they fit the size limit beside
+    the `other_bytes` written anyway, else a fixed sample drawn from numpy's generator seeded 0 (the same pairs on every run)."""
+    k = max(0, (limit - other_bytes - 64 * 1024) // pair_bytes)          # (64 KiB: the .npy headers)
+    if k >= n_pairs:
+        return np.arange(n_pairs)
+    return np.sort(np.random.default_rng(0).choice(n_pairs, size=k, replace=False))
+
+
+def dump_outputs(out_dir, last, keep, m):
+    """What register_batch hands its caller for every pair of the timed path's last step -- (warped source cloud, iter_cnt: loss
+    evaluations per level) -- as .npy files:
+      warped.npy        float32 [k, n, 3]  warped source points of the pairs in warped_pairs.npy
+      warped_pairs.npy  float64 [k]        their indices in the step (dump_selection: all pairs, or a seeded sample within the size limit)
+      iter_cnt.npy      float64 [pairs, m] iter_cnt of every pair of the step, level by level
+    -> {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"warped": np.stack([last[i][0].detach().float().cpu().numpy() for i in keep]).astype(np.float32),
+              "warped_pairs": np.asarray(keep, dtype=np.float64),
+              "iter_cnt": np.array([[ic[lvl] for lvl in range(m)] for _, ic in last], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: become `torch.distributed.run --nproc-per-node N bench.py <same args>`
     (one process per GPU, rendezvous on 127.0.0.1 at a free port) and exit with its status."""
@@ -449,7 +482,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=0, help="ticks between host polls (0: 4, or 8 for the landmark configuration E whose ticks are "
                                                           "four times shorter -- the per-chunk host work of three lanes must fit under one chunk of GPU work)")
     ap.add_argument("--engines", type=int, default=3, help="independent engines (HIP streams) per GPU, `slots` pairs each (3 x 128 until round 3, 2 x 256 in "
-                                                             "round 4; 3 x 256 since round 5: +2.7 % over 2 x 256 in three alternating 4-step runs each, "
+                                                             "round 4; 3 x 256 since round 5: +2.7 %% over 2 x 256 in three alternating 4-step runs each, "
                                                              "profiles/r05_engines_sweep_long.txt)")
     ap.add_argument("--config", default="A", choices=list("ABCDE"),
                     help="SURVEY 8(d) workload: A NDP.yaml faithful (the headline line); B fixed work (= --fixed-work); C samples = 8192; "
@@ -466,14 +499,20 @@ def main():
                          "2 one-pass with the distances on the bf16 matrix pipe and exact re-evaluation (bit-identical results)")
     ap.add_argument("--drain-between-steps", action="store_true", help="one register_batch call per step (every step fills and drains the slots: "
                                                                         "rounds 1-4) instead of the steps as one stream of pairs")
-    ap.add_argument("--no-alt", action="store_true", help="skip the second measurement in the other arithmetic configuration")
-    ap.add_argument("--alt-steps", type=int, default=2, help="timed steps of the second measurement (1 warm-up step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 register() latency measurement")
+    ap.add_argument("--full", action="store_true", help="besides the headline: accuracy of the last step's pairs, the other arithmetic "
+                                                         "configuration, rooflines, surface-pair accuracy, batch-1 latency, CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the second measurement in the other arithmetic configuration")
+    ap.add_argument("--alt-steps", type=int, default=2, help="(--full) timed steps of the second measurement (1 warm-up step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the rooflines and the surface-pair accuracy")
+    ap.add_argument("--no-latency", action="store_true", help="(--full) skip the batch-1 register() latency measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/*.npy "
+                                                                         "(rank 0; see dump_outputs)")
     ap.add_argument("--allow-variant", action="store_true", help="run on an experiment build of the library (deformationpyramid_amd._native."
                                                                   "use_variant); the line records it as `library_variant`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if N.variant() and not args.allow_variant:
         sys.exit(f"bench.py: an experiment build of the library is selected ({N.variant()}); pass --allow-variant to time it")
 
@@ -564,8 +603,10 @@ def main():
 
     host_cpu = {}
 
-    def timed_run(model, steps, warmup):
-        """`warmup` untimed + exactly `steps` timed register_batch passes over the resident pairs, bracketed by barrier + synchronize."""
+    def timed_run(model, steps, warmup, keep=None):
+        """`warmup` untimed + exactly `steps` timed register_batch passes over the resident pairs, bracketed by barrier + synchronize.
+        -> (seconds, Adam steps, loss evaluations, last): last[i] = (warped, iter_cnt) of pair i in the last pass, as register_batch
+        returns it; warped is kept for the pairs in the set `keep` only (None: all), None for the others."""
         torch.manual_seed(rank)
         for _ in range(warmup):
             model.register_batch(pairs, slots=B, chunk=args.chunk, engines=args.engines)
@@ -583,19 +624,24 @@ def main():
             # the K steps as ONE stream of K x pairs_per_step pairs: a slot that frees up at the end of step k takes the first pair of
             # step k + 1 (a service fed by a queue never drains between batches; round 4 filled and drained 512 slots per step).  The
             # step stays the unit of work and of reporting: exactly `steps` passes over the resident pairs, each pair's full
-            # register() -- the results of the last pass are kept for the accuracy block, the others handed to a sink and dropped
+            # register() -- the results of the last pass are kept (for the accuracy block / --dump-outputs), the others handed to a
+            # sink and dropped
             last = [None] * len(pairs)
             first_of_last = (steps - 1) * len(pairs)
 
             def sink(i, warped, state):
-                if i >= first_of_last:
-                    last[i - first_of_last] = (warped, None)
+                j = i - first_of_last
+                if j >= 0:
+                    last[j] = (warped if keep is None or j in keep else None, state)
             model.register_batch(pairs * steps, slots=B, chunk=args.chunk, engines=args.engines, sink=sink)
             n_steps = sum(s.total_steps for s in model.last_states)
             n_evals = sum(s.total_evals for s in model.last_states)
         barrier()
         host_cpu["s"] = time.process_time() - c0
-        return time.perf_counter() - t0, n_steps, n_evals, last
+        elapsed = time.perf_counter() - t0
+        if not args.drain_between_steps:                        # the iteration counts register_batch returns, from the kept states
+            last = [(w, {lvl: int(st.evals_per_level[lvl]) for lvl in range(model.config.m)}) for w, st in last]
+        return elapsed, n_steps, n_evals, last
 
     def accuracy_sums(last):
         keys = msum = None
@@ -606,12 +652,20 @@ def main():
             msum = v if msum is None else msum + v
         return keys, msum
 
+    # the last step's warped clouds are kept for the accuracy block (--full: all of them) and for --dump-outputs (a sample within its
+    # size limit; the same pairs on every run); a plain run keeps none
+    dump_keep = None
+    if args.dump_outputs and rank == 0:
+        n_src = int(pairs[0][0].shape[0])
+        dump_keep = dump_selection(NP, 12 * n_src, 8 * NP * cfg.m)
+    keep = None if args.full else set(dump_keep.tolist() if dump_keep is not None else [])
     model = Registration(cfg, gemm_mode=None if args.gemm_mode < 0 else args.gemm_mode, nn_mode=None if args.nn_mode < 0 else args.nn_mode)
-    elapsed, steps_total, evals_total, last = timed_run(model, args.steps, args.warmup)
+    elapsed, steps_total, evals_total, last = timed_run(model, args.steps, args.warmup, keep=keep)
     host_cpu_main = host_cpu["s"]
     eng0 = model._engines[0]
     main_modes = (eng0.gemm_mode, eng0.nn_mode)
-    keys, msum = accuracy_sums(last)                          # accuracy of the last step's pairs (not timed)
+    dumped = dump_outputs(args.dump_outputs, last, dump_keep, cfg.m) if dump_keep is not None else None
+    keys, msum = accuracy_sums(last) if args.full else ([], [])      # accuracy of the last step's pairs (not timed)
 
     # the single collective (RCCL): one SUM all-reduce carries the sums, every rank's pair count and every rank's elapsed time
     job = job_summary(args.steps * NP, elapsed, [float(steps_total), float(evals_total)] + list(msum) + [float(NP)],
@@ -644,7 +698,6 @@ def main():
         "ms_per_iter": 1e3 * elapsed * n_gpus / max(n_steps, 1.0),
         "adam_iters_per_pair": n_steps / n_pairs,
         "loss_evals_per_pair": n_evals / n_pairs,
-        "accuracy": metrics,
         # what one rank costs the HOST (rank 0's process CPU time over its timed region: main thread, engine steppers, pair
         # producers): the 8-GPU readiness figure -- ranks x host_cores_busy must fit the node's cores / the container's quota
         "host_cpu_s_per_pair": host_cpu_main / (args.steps * NP),
@@ -656,8 +709,12 @@ def main():
                   "elapsed_s": [round(t, 4) for t in job["elapsed_per_rank"]], "allreduce_ms": job["allreduce_ms"],
                   "cpu_placement_rank0": placement},
     }
+    if args.full:
+        out["accuracy"] = metrics
+    if dumped is not None:
+        out["dump_outputs"] = {"files": dumped, "pairs_of_the_last_step": "all" if len(dump_keep) == NP else f"{len(dump_keep)} of {NP} (seeded sample)"}
 
-    single = rank == 0 and n_gpus == 1
+    single = rank == 0 and n_gpus == 1 and args.full             # the measurements beyond the headline: --full only
     if single and not args.no_roofline:
         out.update(roofline_report(model, pairs, B, args.config))
     if single and not args.no_alt and args.config == "A" and main_modes[0] in (0, 7):

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -16,7 +17,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (one warm-up step: on a fresh box the first step pays module loads and first launches, which made the rate comparisons below
 #  fail once in a while)
-SMALL = ["--steps", "2", "--warmup", "1", "--pairs-per-step", "48", "--slots", "24", "--engines", "1",
+# (--full: the accuracy block of the last step's pairs, compared across the rank layouts below, is not part of a plain run)
+SMALL = ["--steps", "2", "--warmup", "1", "--pairs-per-step", "48", "--slots", "24", "--engines", "1", "--full",
          "--no-cpu-baseline", "--no-roofline", "--no-latency", "--no-alt"]
 
 
@@ -67,13 +69,13 @@ def test_bench_rccl_branch_runs_on_one_rank(one_rank):
 
 
 def test_bench_line_carries_both_arithmetic_configurations():
-    """The ONE line of the default run holds the headline measurement and, under `alt`, the same workload in the other
+    """The ONE line of the --full run holds the headline measurement and, under `alt`, the same workload in the other
     arithmetic configuration (bitwise fp32-MFMA kernels <-> bf16-split kernels + matrix-pipe NN), each with the roofline of
     its own dominant kernel priced against the peak of the pipe it runs on."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     rec = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--pairs-per-step", "256", "--slots", "128",
-                "--engines", "1", "--alt-steps", "1", "--no-cpu-baseline", "--no-latency"])
+                "--engines", "1", "--full", "--alt-steps", "1", "--no-cpu-baseline", "--no-latency"])
     _keep("bench_both_arith.json", rec)
     alt = rec["alt"]
     assert {rec["config"]["gemm_mode"], alt["gemm_mode"]} == {0, 7}
@@ -91,3 +93,24 @@ def test_bench_line_carries_both_arithmetic_configurations():
     # same workload, same early-stop behaviour: iterations per pair agree to a percent, accuracy to a few percent
     assert abs(rec["adam_iters_per_pair"] - alt["adam_iters_per_pair"]) < 0.02 * rec["adam_iters_per_pair"]
     assert abs(rec["accuracy"]["full-epe"] - alt["accuracy"]["full-epe"]) < 0.05 * rec["accuracy"]["full-epe"]
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline without the --full measurements;
+    --dump-outputs writes what register_batch returned for the last step's pairs (float32 / float64, at most 64 MB)."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    out_dir = tmp_path / "dump"
+    rec = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-step", "48", "--slots", "24",
+                "--engines", "1", "--dump-outputs", str(out_dir)])
+    assert rec["steps"] == 3 and rec["unit"] == "pairs/s" and rec["higher_is_better"] is True and rec["dtype"].startswith("f32")
+    assert abs(rec["value"] * rec["ms_per_step"] / 1e3 - 48) < 1e-6 * 48                       # pairs per step / seconds per step
+    assert not {"accuracy", "alt", "roofline", "latency", "cpu_baseline", "accuracy_surface_pairs"} & set(rec)
+    files = {p.name: np.load(p) for p in out_dir.iterdir()}
+    assert set(files) == {"warped.npy", "warped_pairs.npy", "iter_cnt.npy"}
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    np.testing.assert_array_equal(files["warped_pairs.npy"], np.arange(48))                 # 48 pairs fit: all of them
+    w, ic = files["warped.npy"], files["iter_cnt.npy"]
+    assert w.shape == (48, 8192, 3) and np.isfinite(w).all()
+    assert ic.shape == (48, 9) and (ic >= 1).all()                                        # every level of every pair evaluated

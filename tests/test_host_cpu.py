@@ -351,6 +351,27 @@ def test_bench_self_launch_builds_a_one_rank_per_gpu_command(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_within_the_size_limit(tmp_path):
+    """`bench.py --dump-outputs DIR` at the default step (8192 pairs of 8192 points, m = 9): the warped clouds of a seeded sample of
+    the pairs -- the same on every run -- and the iteration counts of all of them, float32 / float64, at most 64 MB together."""
+    import bench
+    n_pairs, n, m = 8192, 8192, 9
+    keep = bench.dump_selection(n_pairs, 12 * n, 8 * n_pairs * m)
+    assert 0 < len(keep) < n_pairs and np.array_equal(keep, bench.dump_selection(n_pairs, 12 * n, 8 * n_pairs * m))
+    assert np.all(np.diff(keep) > 0) and keep[-1] < n_pairs
+    np.testing.assert_array_equal(bench.dump_selection(48, 12 * n, 8 * 48 * m), np.arange(48))
+    kept = set(keep.tolist())
+    last = [(torch.full((n, 3), float(i)) if i in kept else None, {lvl: i + lvl for lvl in range(m)}) for i in range(n_pairs)]
+    shapes = bench.dump_outputs(str(tmp_path), last, keep, m)
+    assert shapes == {"warped": [len(keep), n, 3], "warped_pairs": [len(keep)], "iter_cnt": [n_pairs, m]}
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= bench.DUMP_LIMIT_BYTES
+    w, wp, ic = (np.load(tmp_path / f"{name}.npy") for name in ("warped", "warped_pairs", "iter_cnt"))
+    assert w.dtype == np.float32 and wp.dtype == np.float64 and ic.dtype == np.float64
+    np.testing.assert_array_equal(w[:, 0, 0], keep.astype(np.float32))
+    np.testing.assert_array_equal(wp, keep)
+    np.testing.assert_array_equal(ic, np.arange(n_pairs)[:, None] + np.arange(m)[None, :])
+
+
 def test_register_batch_rejects_mixed_landmark_batches():
     """Pairs with and without landmarks optimise different objectives (registration.py:189-212): one engine cannot
     serve both, and silently running them with the first pair's weights would be wrong."""

@@ -264,16 +264,18 @@ def test_F13_shape_transfer_loop_and_vertex_warp(golden):
     assert np.abs(got - g["warped_vert"]).max() < 1e-5
 
 
-def test_ply_reader_reproduces_the_demo_mesh_numbers(golden):
+def test_ply_reader_reproduces_the_demo_mesh_numbers(golden, tmp_path):
     """meshio.read_ply_ascii against numbers captured from sim3_demo/*.ply (counts, bounding box, total area, checksums).
-    The meshes live in /root/reference and never travel: the check runs where they exist."""
+    The two demo meshes are kept xz-compressed under tests/golden/ and read back as the ASCII files they are."""
+    import lzma
+    import shutil
     from deformationpyramid_amd.meshio import read_ply_ascii
     g = golden("F13_shape_transfer")
-    root = "/root/reference/sim3_demo"
-    if not os.path.isdir(root):
-        pytest.skip("demo meshes are only present in the build container")
     for tag, name in (("src", "AlienSoldier.ply"), ("tgt", "Ortiz.ply")):
-        v, f = read_ply_ascii(os.path.join(root, name))
+        path = tmp_path / name
+        with lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sim3_demo_" + name + ".xz")) as fin, open(path, "wb") as fout:
+            shutil.copyfileobj(fin, fout)
+        v, f = read_ply_ascii(str(path))
         assert [v.shape[0], f.shape[0]] == list(g[f"mesh.{tag}.counts"])
         np.testing.assert_array_equal(np.stack([v.min(0), v.max(0)]), g[f"mesh.{tag}.bbox"])
         a, b, c = (v[f[:, k]].astype(np.float64) for k in range(3))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything kept under profiles/ for one round, in one gpurun call (results land in gpurun_out/<tag>_*):
-#   bench lines of SURVEY 8(d) configs A..E (the default line carries BOTH arithmetics: `value` = the default split path, `alt` = the
+#   bench lines of SURVEY 8(d) configs A..E (the --full line carries BOTH arithmetics: `value` = the default split path, `alt` = the
 #   bitwise fp32-MFMA path), rocprofv3 kernel stats of the roofline workload (128 pairs per engine tick) in both arithmetics and of
 #   the batch-1 tick, PMC HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) and the SQ counters, both arithmetics.
 #   usage (on the GPU box): bash tools/profile_round.sh r03
@@ -9,11 +9,11 @@ TAG=${1:-rXX}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_line.err
+python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_line.err
 for c in B C D E; do
-  python bench.py --config $c --steps 2 --warmup 1 > $O/${TAG}_bench_config_$c.json 2> $O/${TAG}_bench_config_$c.err
+  python bench.py --full --config $c --steps 2 --warmup 1 > $O/${TAG}_bench_config_$c.json 2> $O/${TAG}_bench_config_$c.err
 done
-python bench.py --slots 64 --engines 1 --pairs-per-step 2048 --steps 2 --warmup 1 --no-alt --no-latency --no-cpu-baseline > $O/${TAG}_bench_batch64.json 2> /dev/null
+python bench.py --full --slots 64 --engines 1 --pairs-per-step 2048 --steps 2 --warmup 1 --no-alt --no-latency --no-cpu-baseline > $O/${TAG}_bench_batch64.json 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
 # rocprofv3 kernel stats of the tick: default (split) arithmetic, then the bitwise one
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof_tick -o tick -- python $R/tools/tick_bench.py 128 24 > $O/${TAG}_prof_tick.log 2>&1

@@ -63,19 +63,13 @@ static_assert(64 * NDP_W * 4 == BF_REGION, "an fp32 tile fills a region");
 static constexpr int kSmemBwdFBytes = BF_TOTAL;
 static_assert(kSmemBwdFBytes <= 160 * 1024, "fused backward LDS carve");
 
-// BF_OVFL (round 6; -2 % at 256 pairs, bitwise in range: profiles/r06_bwd_ovfl_ab.txt): the tile loop runs with MODE.FP16_OVFL = 1 -- a conversion to fp16 that overflows gives +-65504 instead of inf -- so the
-// gradient splits of the tile loop drop their v_med3 bound (one vector instruction per element; the bits differ only where a scaled
-// gradient exceeds 65504, i.e. 128 times its pair's largest |dO|: hi = 65504 either way, lo = the bounded remainder instead of 0)
-#ifndef BF_OVFL
-#define BF_OVFL 1
-#endif
+// The tile loop runs with MODE.FP16_OVFL = 1 -- a conversion to fp16 that overflows gives +-65504 instead of inf -- so the gradient
+// splits of the tile loop drop their v_med3 bound (one vector instruction per element; the bits differ only where a scaled gradient
+// exceeds 65504, i.e. 128 times its pair's largest |dO|: hi = 65504 either way, lo = the bounded remainder instead of 0).  Measured
+// against the bounded split in round 6 (a compile-time knob, since retired): -2 % at 256 pairs, bitwise in range (profiles/r06_bwd_ovfl_ab.txt).
 __device__ __forceinline__ void bf_split_g(float x, _Float16 &hi, _Float16 &lo) {
-#if BF_OVFL
     hi = (_Float16)x;
     lo = (_Float16)(x - (float)hi);
-#else
-    bf_split<false>(x, hi, lo);
-#endif
 }
 // four float4 of a [64][128] fp32 tile per thread (rows (t >> 5) + 16 i, columns 4 (t & 31) ..), times `scale` -> the two planes
 template <bool ACT>
@@ -203,19 +197,7 @@ __device__ __forceinline__ void bf_load_wt(const float *W /*[o][k]*/, int wv, in
 
 // dW[2 blocks] += (S dz)^T (2^6 h) over the 64 points of the planes at byte offsets rz / rh of the LDS (wave: o-block ob, k-blocks kb,
 // kb + 1), one accumulator per block
-// (round 6) f.gap(i) runs BEHIND product i (0..23), between scheduling barriers: five or six vector instructions ride free in the
-// shadow of a 32x32x16 (tools/experiments/micro/coexec2.hip) -- also behind a DEPENDENT one, whose successor cannot issue before it
-// retires anyway; what the gaps carry is work that does not depend on this contraction (layer 2: the recomputation of h0; layer 1:
-// the next tile's requests and small rows).
-#ifndef BF_INTERLEAVE
-#define BF_INTERLEAVE 0
-#endif
-#ifndef BF_H1REQ
-#define BF_H1REQ 1                                  /* where stage 4 requests the next tile's h1 image: 1 between its two contractions, 0 at its end */
-#endif
-struct BfNoFill { __device__ __forceinline__ void gap(int) {} };
-template <class F>
-__device__ __forceinline__ void bf_wgrad(const _Float16 *lds, int rz, int rh, const BfOffs &o, f32x16 (&acc)[2], F &f) {
+__device__ __forceinline__ void bf_wgrad(const _Float16 *lds, int rz, int rh, const BfOffs &o, f32x16 (&acc)[2]) {
     const int za = bf_base(rz, o.tr[0][0]), zb = bf_base(rz, o.tr[0][1]);
     const int h0a = bf_base(rh, o.tr[1][0]), h0b = bf_base(rh, o.tr[1][1]), h1a = bf_base(rh, o.tr[2][0]), h1b = bf_base(rh, o.tr[2][1]);
     // eight steps s = 2 ks + m (k-step, block); the fragments of step s + 1 are requested before the three products of step s issue
@@ -236,15 +218,9 @@ __device__ __forceinline__ void bf_wgrad(const _Float16 *lds, int rz, int rh, co
         __builtin_amdgcn_sched_barrier(0);
         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[ks & 1][1], B[st & 1][0], acc[m], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        f.gap(3 * st);
-        __builtin_amdgcn_sched_barrier(0);
         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[ks & 1][0], B[st & 1][1], acc[m], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        f.gap(3 * st + 1);
-        __builtin_amdgcn_sched_barrier(0);
         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[ks & 1][0], B[st & 1][0], acc[m], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        f.gap(3 * st + 2);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -253,11 +229,9 @@ __device__ __forceinline__ void bf_wgrad(const _Float16 *lds, int rz, int rh, co
 // group; fr[ks]: the lane's fragment bases of the dz planes (bf_base).  SWAP: operands exchanged -- the accumulator then holds feature
 // 16 wv + l15 of points 16 g + 4 lk + r.  Software-pipelined: the fragments of step s + 1 (s = 4 g + ks) are requested before the
 // products of step s issue.  The epilogue of a group -- mask, split, stores -- comes as TWELVE steps epi(g, d, k), k = 0..11, of two
-// or three vector instructions each: DEAL (round 6) places step k of group g - 1 behind product k of group g (two vector
-// instructions hide in a 16x16x32 gap), group 0's gaps carry f0.gap(k), and only the last group's epilogue is in the open; without
-// DEAL the twelve steps follow the first three products of the next group in a block (round 4's order: same results).
-template <bool SWAP, bool DEAL, class Epi, class F0>
-__device__ __forceinline__ void bf_dgrad_tile(const h16x8 (&wt)[2][4], const _Float16 *lds, const int (&fr)[4], Epi epi, F0 &f0) {
+// or three vector instructions each, which follow the first three products of the next group in a block.
+template <bool SWAP, class Epi>
+__device__ __forceinline__ void bf_dgrad_tile(const h16x8 (&wt)[2][4], const _Float16 *lds, const int (&fr)[4], Epi epi) {
     h16x8 Bf[2][2];
     auto fetch = [&](int st) {
         const _Float16 *rp = lds + fr[st & 3] + 16 * (st >> 2) * BF_ROW;
@@ -279,19 +253,12 @@ __device__ __forceinline__ void bf_dgrad_tile(const h16x8 (&wt)[2][4], const _Fl
             for (int pd = 0; pd < 3; ++pd) {                         // lo.hi, hi.lo, hi.hi
                 const h16x8 &bz = Bf[st & 1][pd == 1 ? 1 : 0], &wz = wt[pd == 0 ? 1 : 0][ks];
                 d = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_f16(bz, wz, d, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_f16(wz, bz, d, 0, 0, 0);
-                if (DEAL) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (g == 0) f0.gap(3 * ks + pd); else epi(g - 1, dp, 3 * ks + pd);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
             }
-            if (!DEAL) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == 0 && g > 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks == 0 && g > 0) {
 #pragma unroll
-                    for (int k = 0; k < 12; ++k) epi(g - 1, dp, k);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                for (int k = 0; k < 12; ++k) epi(g - 1, dp, k);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         dp = d;
@@ -321,44 +288,6 @@ __device__ __forceinline__ B8Scale bf_scale(const ndp_engine &e, int b) {
     return r;
 }
 
-// ---- VARIANT (gemm_mode bit 64, measured in round 4): the Adam step of the pair applied by the LAST of its backward workgroups to
-// arrive, instead of the k_eng_update launch.  One ticket per workgroup (agent-scope release before it, acquire after); the last
-// arriver folds the G partials in index order -- the update kernel's order, so the results are bitwise the same -- and steps all P
-// parameters with its 512 threads.  e.gmax[B + b] holds the pair's ticket (left at zero for the next tick).
-__device__ __forceinline__ void bf_pair_update(const ndp_engine &e, int b, const ndp_pair_state &ns, int t, int n_threads) {
-    const ndp_layer_desc dl = desc_at_level(e.desc, ns.step_level);
-    const int pc = ndp_param_count(&dl);
-    float *m = e.adam_m + (size_t)b * e.p_stride, *v = e.adam_v + (size_t)b * e.p_stride;
-    const float *gp = e.gpart + (size_t)b * e.G * e.p_stride;
-    float *p = e.params + ((size_t)b * e.m + ns.step_level) * e.p_stride;
-    const float ns0 = e.adam_tab[2 * ns.step_t], ns1 = e.adam_tab[2 * ns.step_t + 1];
-    const bool step = ns.decision != NDP_DEC_ADVANCE, fresh = ns.decision != NDP_DEC_STEP;
-    for (int i0 = t; i0 < e.P; i0 += 4 * n_threads) {                 // four parameters in flight per thread
-        float g[4], pi[4], mi[4], vi[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * n_threads;
-            g[u] = 0.f; pi[u] = 0.f; mi[u] = 0.f; vi[u] = 0.f;
-            if (i < pc && step) {
-                g[u] = gp[i];
-                for (int k = 1; k < e.G; ++k) g[u] += gp[(size_t)k * e.p_stride + i];
-                pi[u] = p[i]; mi[u] = m[i]; vi[u] = v[i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * n_threads;
-            if (i >= e.P) continue;
-            if (i < pc && step) {
-                adam_update(pi[u], g[u], mi[u], vi[u], e.adam_w1, e.adam_b2, e.adam_w2, ns0, ns1, e.adam_eps);
-                p[i] = pi[u];
-                if (!fresh) { m[i] = mi[u]; v[i] = vi[u]; }
-            }
-            if (fresh) { m[i] = 0.f; v[i] = 0.f; }                     // registration.py:176 (and the gate row a level-0 step does not have)
-        }
-    }
-}
-
 // dz2 before its mask: a[i][c] = sum_j Wh[j][4 (t & 31) + c] (S dO)[row (t >> 5) + 16 i][j], the fp32 fma chain from zero, j ascending
 // (NH > 0: the head count as a compile-time constant; 0: nh at run time)
 template <int NH>
@@ -385,7 +314,7 @@ __device__ __forceinline__ void bf_dz2_chain(const float *whs, const float *dr, 
 // all but eight of the update stage's 136 workgroups per pair;
 // the arithmetic is eng_update_param's (ONE partial: its fold is the identity): same bits.  noinline: the tile loop keeps its registers.
 __host__ __device__ inline bool bf_adam_in_tail(const ndp_engine &e) {
-    return e.G == 1 && (e.gemm_mode & 7) == 7 && !(e.gemm_mode & (16 | 64 | 256 | 1024));
+    return e.G == 1 && (e.gemm_mode & 7) == 7 && !(e.gemm_mode & (16 | 1024));
 }
 // (scalars and pointers by value: a reference to the engine record would put the whole kernel argument on the stack)
 struct BfAdamK { float w1, b2, w2, eps, ns0, ns1; };
@@ -423,8 +352,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
     const int off_W0 = ndp_off_W0(&dd), off_b0 = ndp_off_b0(&dd), off_W1 = ndp_off_Wi(&dd, 1), off_b1 = ndp_off_bi(&dd, 1);
     const int off_W2 = ndp_off_Wi(&dd, 2), off_b2 = ndp_off_bi(&dd, 2), off_Wh = ndp_off_Wi(&dd, 3);
     Bwd8Setup j;
-    const bool fold_update = (e.gemm_mode & 64) != 0;
-    int &s_ticket = *reinterpret_cast<int *>(smb + BF_PEQ);          // (bit 64 only; the region is dead wherever the ticket is drawn)
     if (!eng_bwd8_setup(e, parity, 0, e.P, j)) {
         if (bf_adam_in_tail(e) && e.state[(size_t)(parity ^ 1) * e.B + blockIdx.y].decision == NDP_DEC_ADVANCE) {
             // no step, fresh moments for the next level (registration.py:176): the two matrices' here, the rest in k_eng_update_rest
@@ -433,23 +360,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
             for (int i = threadIdx.x; i < NDP_W * NDP_W / 4; i += 512) {
                 reinterpret_cast<float4 *>(m + off_W1)[i] = z; reinterpret_cast<float4 *>(v + off_W1)[i] = z;
                 reinterpret_cast<float4 *>(m + off_W2)[i] = z; reinterpret_cast<float4 *>(v + off_W2)[i] = z;
-            }
-        }
-        if (fold_update) {
-            const ndp_pair_state ns0 = e.state[(size_t)(parity ^ 1) * e.B + blockIdx.y];
-            if (ns0.decision == NDP_DEC_ADVANCE) {                     // no step, fresh moments for the next level: every workgroup a slice
-                float *m = e.adam_m + (size_t)blockIdx.y * e.p_stride, *v = e.adam_v + (size_t)blockIdx.y * e.p_stride;
-                for (int i = blockIdx.x * 512 + threadIdx.x; i < e.P; i += gridDim.x * 512) { m[i] = 0.f; v[i] = 0.f; }
-            } else if (ns0.decision != NDP_DEC_IDLE) {                 // a workgroup without a tile: its (zeroed) partial still counts
-                __threadfence();
-                __syncthreads();
-                if (threadIdx.x == 0) s_ticket = atomicAdd(e.gmax + e.B + blockIdx.y, 1u);
-                __syncthreads();
-                if (s_ticket == (int)gridDim.x - 1) {
-                    __threadfence();
-                    bf_pair_update(e, blockIdx.y, ns0, threadIdx.x, 512);
-                    if (threadIdx.x == 0) e.gmax[e.B + blockIdx.y] = 0u;
-                }
             }
         }
         return;
@@ -554,9 +464,7 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
     __syncthreads();
     dO_stage(t);
     PT(10);
-#if BF_OVFL
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");      // MODE.FP16_OVFL for the tile loop (restored behind it)
-#endif
     int par = 0;
     for (int tile = j.tile0; tile < j.n_tiles; tile += j.tile_step, par ^= 1) {
         const int base = tile * NDP_TILE;
@@ -647,17 +555,16 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
         if (tile + j.tile_step < j.n_tiles) dma_dO(tile + j.tile_step);       // the next tile's dO rows (this tile's are dead since stage 2): in by stage 4,
                                                                               //   where dO_stage works on them
         // ---- stage 3: layer 2 -- weight gradient, data gradient -> S dz1 planes -- and h0 = relu(z0) -> 2^6 h0 planes (from the packed
-        //      encoding rows written before the barrier above).  Order (round 6, BF_INTERLEAVE): the recomputation of h0 rides in the 24
-        //      gaps of the weight gradient (one step of <= 6 vector instructions per gap: per point group a read, layer 0's MFMA, two
-        //      steps of activation + mask floor, two of split + stores), the epilogue of point group g - 1 of the data gradient in the
-        //      gaps of group g; only the last group's epilogue is in the open.
+        //      encoding rows written before the barrier above), ahead of the weight gradient.  Round 6 measured the recomputation in the
+        //      24 MFMA gaps of the weight gradient and each data-gradient epilogue dealt over the next point group's gaps (a
+        //      compile-time knob, since retired): same bits, no gain (profiles/r06_bwd_steps_ab.txt); the steps of h0_step are its unit.
         typedef float f32x2v __attribute__((ext_vector_type(2)));
         h16x8 h0_b; f32x4v h0_z; f32x2v h0_y[2]; h16x2 h0_hi[2];
-        auto h0_step = [&](int i) {                                  // step i = 6 g + s of the recomputation (bitwise f8_l0_group + bf_act<true> + bf_store4)
+        auto h0_step = [&](int i) {                                  // step i = 6 g + s of the recomputation (bitwise f8_l0_group + bf_act_s + bf_store4)
             const int g = i / 6, sx = i - 6 * g;
             if (sx == 0) h0_b = *reinterpret_cast<const h16x8 *>(l0rows + (16 * g + l15) * F8_L0ROW + 8 * lk);
             else if (sx == 1) { const f32x4v zero = {0.f, 0.f, 0.f, 0.f}; h0_z = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0.a, h0_b, zero, 0, 0, 0); }
-            else if (sx < 4) { const int q = sx - 2; h0_y[q][0] = F8_SIGNMASK ? bf_act_s(h0_z[2 * q]) : bf_act<true>(h0_z[2 * q]); h0_y[q][1] = F8_SIGNMASK ? bf_act_s(h0_z[2 * q + 1]) : bf_act<true>(h0_z[2 * q + 1]); }   // 2^6 h0, bounded; its mask in hi's sign
+            else if (sx < 4) { const int q = sx - 2; h0_y[q][0] = bf_act_s(h0_z[2 * q]); h0_y[q][1] = bf_act_s(h0_z[2 * q + 1]); }   // 2^6 h0, bounded; its mask in hi's sign
             else if (sx == 4) { h0_hi[0] = __builtin_convertvector(h0_y[0], h16x2); h0_hi[1] = __builtin_convertvector(h0_y[1], h16x2); }
             else {
                 const h16x2 l0 = __builtin_convertvector(h0_y[0] - __builtin_convertvector(h0_hi[0], f32x2v), h16x2);
@@ -669,7 +576,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
                 *reinterpret_cast<h16x4 *>(dst + BF_PLANE) = P1;
             }
         };
-        struct H0Fill { decltype(h0_step) &st; __device__ __forceinline__ void gap(int i) { st(i); } } h0_fill{h0_step};
         // the epilogue of a point group of either data gradient: S dz = d / 2^6 where the activation's hi part is > 0 (the compare on the
         // fp16 itself), bounded, split -- in twelve steps (bf_dgrad_tile); e_* is its state between the steps
         f32x2v e_z[2]; h16x2 e_hi[2]; h16x4 e_hm; _Float16 e_m[4];
@@ -677,9 +583,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
             if (k == 1) { e_z[0][0] = d[0] * inv_w; e_z[0][1] = d[1] * inv_w; e_z[1][0] = d[2] * inv_w; e_z[1][1] = d[3] * inv_w; }
             else if (k == 6 || k == 7) {
                 const int q = k - 6;
-#if !BF_OVFL
-                e_z[q][0] = __builtin_amdgcn_fmed3f(e_z[q][0], -65504.0f, 65504.0f); e_z[q][1] = __builtin_amdgcn_fmed3f(e_z[q][1], -65504.0f, 65504.0f);
-#endif
                 e_hi[q] = __builtin_convertvector(e_z[q], h16x2);
             } else if (k == 8 || k == 9) { const int q = k - 8; e_z[q] = e_z[q] - __builtin_convertvector(e_hi[q], f32x2v); }   // -> the lo parts, still fp32
         };
@@ -702,30 +605,22 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
                 *reinterpret_cast<h16x4 *>(dst + BF_PLANE) = P1;
             } else epi_common(d, k);
         };
-        BfNoFill nofill;
         const int fr2[4] = {bf_base(rD, offs.fr[0]), bf_base(rD, offs.fr[1]), bf_base(rD, offs.fr[2]), bf_base(rD, offs.fr[3])};
-#if BF_INTERLEAVE
-        bf_wgrad(lds16, rD, rC, offs, dW2, h0_fill);
-        __builtin_amdgcn_sched_barrier(0);
-        bf_dgrad_tile<false, true>(wt2, lds16, fr2, epi2, nofill);
-#else
 #pragma unroll
         for (int i = 0; i < 24; ++i) h0_step(i);
         __builtin_amdgcn_sched_barrier(0);
-        bf_wgrad(lds16, rD, rC, offs, dW2, nofill);
+        bf_wgrad(lds16, rD, rC, offs, dW2);
         __builtin_amdgcn_sched_barrier(0);
-        bf_dgrad_tile<false, false>(wt2, lds16, fr2, epi2, nofill);
-#endif
+        bf_dgrad_tile<false>(wt2, lds16, fr2, epi2);
         PTF(6);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the next tile's dO rows (nothing else is out in this stage)
         __syncthreads();
         PT(7);
         // ---- stage 4: layer 1 -- weight gradient, data gradient -> dz0 -> [dW0 | db0]; the next tile's h2 image into the region layer 2 has
-        //      finished with, its encodings, and dO_stage on its dO rows -- in the gaps of the weight gradient (BF_INTERLEAVE), as is the
-        //      data gradient's epilogue in its own gaps
+        //      finished with, its encodings, and dO_stage on its dO rows -- ahead of the weight gradient
         const bool has_next = tile + j.tile_step < j.n_tiles;
         float4 n_vo, n_g;
-        auto next_step = [&](int i) {                                // gap i of the weight gradient
+        auto next_step = [&](int i) {                                // step i of the next tile's preparation
             if (!has_next) return;
             const int nt = tile + j.tile_step;
             if (i < 4) {                                             // h2 image of the next tile over this tile's dz2 planes: 4 x 1 KiB per wave
@@ -749,7 +644,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
                 }
             }
         };
-        struct NextFill { decltype(next_step) &st; __device__ __forceinline__ void gap(int i) { st(i); } } next_fill{next_step};
         // The data gradient with its operands SWAPPED (A = the dz1 fragment, B = the weight slice): the accumulator then holds
         // feature 16 wv + l15 of points 16 g + 4 lk + r -- which is the A-operand layout of a 16x16x32 MFMA whose contraction runs
         // over the points: two groups fill the eight slots of a lane, and [dW0 | db0] += (S dz0)^T [pe | 1] is three products per
@@ -781,33 +675,20 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
             } else epi_common(d, k);
         };
         const int fr1[4] = {bf_base(rB, offs.fr[0]), bf_base(rB, offs.fr[1]), bf_base(rB, offs.fr[2]), bf_base(rB, offs.fr[3])};
-#if BF_INTERLEAVE
-        bf_wgrad(lds16, rB, rA, offs, dW1, next_fill);
-        __builtin_amdgcn_sched_barrier(0);
-        bf_dgrad_tile<true, true>(wt1, lds16, fr1, epi1, nofill);
-#else
 #pragma unroll
         for (int i = 0; i < 10; ++i) next_step(i);
-        bf_wgrad(lds16, rB, rA, offs, dW1, nofill);
+        bf_wgrad(lds16, rB, rA, offs, dW1);
         __builtin_amdgcn_sched_barrier(0);
-#if BF_H1REQ == 1
         // the next tile's h1 image, BETWEEN the stage's two contractions (round 6): the h2 image, which must land within this stage, still
         // has a head start of the weight gradient, and h1 -- read in stage 3 -- no longer has only stages 1-2 to arrive in, which this round
-        // made 40 % shorter (at the end of the stage, round 4's place: +1.3 % at 256 pairs, profiles/r06_bwd_h1req_ab.txt)
+        // made 40 % shorter (requested at the end of the stage, round 4's place, a compile-time knob since retired: +1.3 % at 256 pairs,
+        // profiles/r06_bwd_h1req_ab.txt)
         if (has_next) dma_rows(1, tile + j.tile_step, rC);
         __builtin_amdgcn_sched_barrier(0);
-#endif
-        bf_dgrad_tile<true, false>(wt1, lds16, fr1, epi1, nofill);
-#endif
-#if BF_H1REQ != 1 || BF_INTERLEAVE
-        if (has_next) dma_rows(1, tile + j.tile_step, rC);           // the next tile's h1 image, BEHIND this stage's own work: the h2
-                                                                     //   image had the stage to itself, and h1 has until stage 3
-#endif
+        bf_dgrad_tile<true>(wt1, lds16, fr1, epi1);
         PTF(9);
     }
-#if BF_OVFL
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0");
-#endif
     // ---- the workgroup's gradient partial
     t = t0; lane = t & 63; wv = t >> 6; l15 = lane & 15; lk = lane >> 4; l31 = lane & 31; h = lane >> 5; ob = wv & 3; kb = 2 * (wv >> 2);
     float *G = j.gpart;
@@ -870,17 +751,6 @@ __device__ __forceinline__ void eng_bwd_f_stage(const ndp_engine &e, int parity,
         const BfAdamK ak = {e.adam_w1, e.adam_b2, e.adam_w2, e.adam_eps, e.adam_tab[2 * step_t], e.adam_tab[2 * step_t + 1]};
         bf_adam_tail(e.params + ((size_t)blockIdx.y * e.m + step_level) * e.p_stride, e.adam_m + (size_t)blockIdx.y * e.p_stride,
                      e.adam_v + (size_t)blockIdx.y * e.p_stride, ak, nsp->decision != NDP_DEC_STEP ? 1 : 0, gl, off_W2, off_W1);
-    }
-    if (fold_update) {
-        __threadfence();                                             // this workgroup's partial is visible device-wide before its ticket
-        __syncthreads();
-        if (t == 0) s_ticket = atomicAdd(e.gmax + e.B + blockIdx.y, 1u);
-        __syncthreads();
-        if (s_ticket == (int)gridDim.x - 1) {
-            __threadfence();
-            bf_pair_update(e, blockIdx.y, e.state[(size_t)(parity ^ 1) * e.B + blockIdx.y], t, 512);
-            if (t == 0) e.gmax[e.B + blockIdx.y] = 0u;
-        }
     }
     PT(11);
 }

@@ -43,12 +43,6 @@ typedef short s16x8v __attribute__((ext_vector_type(8)));
 #define B8_ZROW1 168
 #endif
 #define B8_HPLANE (64 * B8_HROW)
-#ifndef B8_PIPE1
-#define B8_PIPE1 false
-#endif
-#ifndef B8_PIPE2
-#define B8_PIPE2 false
-#endif
 enum : int {                              // byte offsets of the dynamic LDS region of the split backward kernels
     B8_PZ = 0,                            // [2][64][F8_ROW] fp16: S dz of the layer
     B8_PH = B8_PZ + 2 * F8_PLANE * 2,     // [2][64][B8_HROW] fp16: the layer's input activation (bwd2 carve; bwd1 has its own below)
@@ -161,27 +155,20 @@ __device__ __forceinline__ void b8_wgrad_frags(const _Float16 *pz, const _Float1
         B[1][s] = tr_frag<B8_HROW>(ph + s * B8_HPLANE, ks, 32 * kb + 32, lane);
     }
 }
-// the transposing reads of k-step ks + 1 are in flight while the six MFMAs of k-step ks run (PIPE; costs 24 registers)
-template <int ZROW, bool PIPE>
+// in the compiler's order (prefetching k-step ks + 1 behind the six MFMAs of k-step ks cost 24 registers: compile-time
+// knobs, not the default, since retired)
+template <int ZROW>
 __device__ __forceinline__ void b8_wgrad(const _Float16 *pz, const _Float16 *ph, int ob, int kb, int lane, f32x16 (&acc)[2][2]) {
-    h16x8 A[2][2], B[2][2][2];
-    if (PIPE) b8_wgrad_frags<ZROW>(pz, ph, 0, ob, kb, lane, A[0], B[0]);
+    h16x8 A[2], B[2][2];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-        const int cur = PIPE ? (ks & 1) : 0;
-        if (PIPE) {
-            if (ks < 3) b8_wgrad_frags<ZROW>(pz, ph, ks + 1, ob, kb, lane, A[cur ^ 1], B[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            b8_wgrad_frags<ZROW>(pz, ph, ks, ob, kb, lane, A[0], B[0]);
-        }
+        b8_wgrad_frags<ZROW>(pz, ph, ks, ob, kb, lane, A, B);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            acc[m][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[cur][1], B[cur][m][0], acc[m][1], 0, 0, 0);
-            acc[m][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[cur][0], B[cur][m][1], acc[m][1], 0, 0, 0);
-            acc[m][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[cur][0], B[cur][m][0], acc[m][0], 0, 0, 0);
+            acc[m][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[1], B[m][0], acc[m][1], 0, 0, 0);
+            acc[m][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[m][1], acc[m][1], 0, 0, 0);
+            acc[m][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[0], B[m][0], acc[m][0], 0, 0, 0);
         }
-        if (PIPE) __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -204,18 +191,13 @@ __device__ __forceinline__ void b8_dgrad_g(const h16x8 (&wt)[2][4], const _Float
     for (int r = 0; r < 4; ++r) d[r] = fmaf(dc[r], F8_LO_WEIGHT, dm[r]) * inv;
 }
 
-#ifndef B8_DPIPE
-#define B8_DPIPE 2                         /* prefetch distance (k-steps) of the pipelined data gradient */
-#endif
-#ifndef B8_DPIPE1
-#define B8_DPIPE1 0                        /* bwd1 keeps the compiler's order: it sits at the 256-register cap and the fragment ring spills (0.092 -> 0.102 ms) */
-#endif
-// The data gradient of a whole tile, software-pipelined like f8_layer (F8_PIPE): the eight B fragments of point group g + 1 are
+// The data gradient of a whole tile (bwd2), software-pipelined like f8_layer (F8_PIPE): the eight B fragments of point group g + 1 are
 // requested before the twelve MFMAs of group g are issued, and the epilogue of group g - 1 -- epi(g, dm, dc, slice), cut into four
-// slices by its caller -- sits between the k-steps of group g, pinned by scheduling barriers.
+// slices by its caller -- sits between the k-steps of group g, pinned by scheduling barriers.  bwd1 keeps the compiler's order
+// (b8_dgrad_g): it sits at the 256-register cap and the fragment ring spilled there (0.092 -> 0.102 ms; a compile-time knob, since retired).
 template <int ZROW, class Epi>
 __device__ __forceinline__ void b8_dgrad_tile(const h16x8 (&wt)[2][4], const _Float16 *pz, int l15, int lk, Epi epi) {
-    constexpr int D = B8_DPIPE, NS = D + 1;                           // fragments of step s + D are requested at step s (s = 4 g + ks)
+    constexpr int D = 2, NS = D + 1;                                  // fragments of step s + D are requested at step s (s = 4 g + ks)
     h16x8 Bf[NS][2];
     f32x4v dm[2], dc[2];
     const _Float16 *rp0 = pz + l15 * ZROW + ((8 * lk) ^ f8_swz(l15));
@@ -377,27 +359,7 @@ k_eng_bwd1_8(ndp_engine e, int parity) {
         }
         __syncthreads();
         if (tile + j.tile_step < j.n_tiles) request(tile + j.tile_step);
-        b8_wgrad<B8_ZROW1, B8_PIPE1>(pz, ph, ob, kb, lane, dW);
-#if B8_DPIPE1
-        {
-            h16x4 hm;
-            float q[6];
-            b8_dgrad_tile<B8_ZROW1>(wt, pz, l15, lk, [&](int g, const f32x4v &dm, const f32x4v &dc, int r) {
-                const int p = 16 * g + l15;
-                if (r == 0) {
-                    hm = *reinterpret_cast<const h16x4 *>(ph + p * B8_HROW + 16 * wv + 4 * lk);  // hi part: > 0 exactly where h0 is
-                    const float4 q0 = *reinterpret_cast<const float4 *>(pes + p * 8);
-                    const float2 q1 = *reinterpret_cast<const float2 *>(pes + p * 8 + 4);
-                    q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y;
-                }
-                const float d = fmaf(dc[r], F8_LO_WEIGHT, dm[r]) * sc.inv;
-                const float z0 = (float)hm[r] > 0.f ? d : 0.f;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) w0acc[r][c] = fmaf(z0, q[c], w0acc[r][c]);
-                w0acc[r][6] += z0;
-            });
-        }
-#else
+        b8_wgrad<B8_ZROW1>(pz, ph, ob, kb, lane, dW);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             f32x4v d;
@@ -415,7 +377,6 @@ k_eng_bwd1_8(ndp_engine e, int parity) {
                 w0acc[r][6] += z0;
             }
         }
-#endif
     }
     float *G = j.gpart;
     b8_store_dW(G + off_W1, dW, sc.inv, ob, kb, l31, h);
@@ -482,16 +443,7 @@ k_eng_bwd2_8(ndp_engine e, int parity) {
         const int base = tile * NDP_TILE;
         __syncthreads();                                             // the previous tile's reads of planes / tile / dO rows are done
         PT(0);
-#if !defined(B2_T_NO_H1SPLIT)                                         /* timing-only variants (tools/phase_timing.py, NDP_PT_STAGE=3) */
         b8_split_rows<B8_HROW, false, false>(v1, ph, t);             // h1 -> planes
-#else
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (t >> 5) + 16 * i, c = 4 * (t & 31);
-            *reinterpret_cast<float2 *>(ph + row * B8_HROW + c) = make_float2(v1[i].x, v1[i].y);
-            *reinterpret_cast<float2 *>(ph + B8_HPLANE + row * B8_HROW + c) = make_float2(v1[i].z, v1[i].w);
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<float4 *>(ft + ((t >> 5) + 16 * i) * NDP_LD + 4 * (t & 31)) = v2[i];   // h2 -> fp32 tile
         if (t < 256) {
@@ -504,7 +456,6 @@ k_eng_bwd2_8(ndp_engine e, int parity) {
         // ---- dWh += dO^T h2 over the tile's 64 points (fp32 MFMA 16x16x4: A = dO[p][j = l15], B = h2[p][16 wv + l15]), HERE: it needs
         // only the h2 tile and the dO rows, and this phase (the dz2 chains, vector pipe only) has the matrix pipe idle (A/B on one box: 0.1437-0.1446 against 0.1476-0.1501 ms
         // with the stage behind the second barrier, in front of the weight-gradient MFMAs)
-#if !defined(B2_T_NO_DWH)
         {                                                           // every operand first (one LDS latency, not four), then the 16 MFMAs
             float oa[16], ob2[16];
 #pragma unroll
@@ -515,7 +466,6 @@ k_eng_bwd2_8(ndp_engine e, int parity) {
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) gWh = MFMA16(oa[ks], ob2[ks], gWh);
         }
-#endif
         PT(5);
         // dz2 of this thread's rows (t >> 5) + 16 i, columns 4 (t & 31) ..: the j = 0 .. nh-1 fma chain from zero, masked by h2 > 0
         float4 z[4];
@@ -542,26 +492,14 @@ k_eng_bwd2_8(ndp_engine e, int parity) {
                 cs.x += z[i].x; cs.y += z[i].y; cs.z += z[i].z; cs.w += z[i].w;
             }
         }
-#if !defined(B2_T_NO_DZ2SPLIT)
         b8_split_rows<F8_ROW, true, true>(z, pz, t, sc.s);
-#else
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = (t >> 5) + 16 * i, c = (4 * (t & 31)) ^ f8_swz(row);
-            *reinterpret_cast<float2 *>(pz + row * F8_ROW + c) = make_float2(z[i].x, z[i].y);
-            *reinterpret_cast<float2 *>(pz + 64 * F8_ROW + row * F8_ROW + c) = make_float2(z[i].z, z[i].w);
-        }
-#endif
         PT(3);
         __syncthreads();
         PT(4);
         if (tile + j.tile_step < j.n_tiles) request(tile + j.tile_step);
-#if !defined(B2_T_NO_WGRAD)
-        b8_wgrad<F8_ROW, B8_PIPE2>(pz, ph, ob, kb, lane, dW);
-#endif
+        b8_wgrad<F8_ROW>(pz, ph, ob, kb, lane, dW);
         PT(6);
         float *zo = j.act + (2 * (size_t)j.plane + base) * NDP_W;     // dz1 replaces h2 in HBM (bwd1 reads it)
-#if B8_DPIPE
         {
             h16x4 hm;
             float o4[4];
@@ -574,18 +512,6 @@ k_eng_bwd2_8(ndp_engine e, int parity) {
                 if (r == 3) *reinterpret_cast<float4 *>(zo + p * NDP_W + 16 * wv + 4 * lk) = make_float4(o4[0], o4[1], o4[2], o4[3]);
             });
         }
-#else
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4v d;
-            b8_dgrad_g<F8_ROW>(wt, pz, g, l15, lk, sc.inv, d);
-            const int p = 16 * g + l15;
-            const h16x4 hm = *reinterpret_cast<const h16x4 *>(ph + p * B8_HROW + 16 * wv + 4 * lk);  // hi part: > 0 exactly where h1 is
-            *reinterpret_cast<float4 *>(zo + p * NDP_W + 16 * wv + 4 * lk) =
-                make_float4((float)hm[0] > 0.f ? d[0] : 0.f, (float)hm[1] > 0.f ? d[1] : 0.f, (float)hm[2] > 0.f ? d[2] : 0.f,
-                            (float)hm[3] > 0.f ? d[3] : 0.f);
-        }
-#endif
         PT(7);
     }
     float *G = j.gpart;

@@ -22,8 +22,8 @@
 //   layer 0 and the heads ride in the layers' MFMA gaps, two barriers per tile); to HBM: h2 as fp32 rows from the registers, h1 as
 //   fp32 rows or -- for the fused backward -- as that kernel's plane image, copied out of the planes in 1 KiB pieces; h0 only for a
 //   backward on the fp32 MFMA; the heads read h2 as planes too.  With one workgroup per CU nothing hides a serial phase, so the per-point warp (one wave, 5.5k cycles of
-//   dependent transcendental latency per tile) is a launch of its own (k_eng_warp: one thread per point, from the saved head record;
-//   same head_warp_fwd code, same bits) unless a workgroup owns a single tile (the batch-1 shape: k_eng_fwd8(.., warp_here)).
+//   dependent transcendental latency per tile) runs behind the workgroup's tile loop, 512 threads wide (eng_warp_tail), unless a
+//   workgroup owns a single tile (the batch-1 shape: its 64 threads warp the tile's points).  Same head_warp_fwd code, same bits.
 // ------------------------------------------------------------------------------------------------
 // Workgroup barrier for LDS hazards only.  __syncthreads() also drains the vector-memory counter (s_waitcnt vmcnt(0)): every barrier
 // of a tile then waits for the activation rows that were just queued for HBM -- nobody in these kernels reads them back.
@@ -90,32 +90,20 @@ __device__ __forceinline__ void bf_split(float x, _Float16 &hi, _Float16 &lo) {
     }
     lo = (_Float16)(x - (float)hi);
 }
-// x' = 2^6 relu(v) saturated at fp16's largest value, from v' = 2^6 v.  MASKED: the hi plane of x' is going to be read as a ReLU mask
-// (hi > 0 wherever v > 0): x' >= 2^-24, fp16's smallest subnormal, wherever v > 0 -- a compare, ONE v_med3 for bound and floor, a
-// select; otherwise one v_med3 (ReLU and the bound together).
-template <bool MASKED>
-__device__ __forceinline__ float bf_act(float vs) {
-    if (!MASKED) return __builtin_amdgcn_fmed3f(vs, 0.f, 65504.0f);
-    const float x = __builtin_amdgcn_fmed3f(vs, 5.9604645e-8f, 65504.0f);
-    return vs > 0.f ? x : 0.f;
-}
-// Round 6, F8_SIGNMASK: the ReLU mask travels in the SIGN of the hi part instead -- hi = -0 where v <= 0, hi >= +0 where v > 0 (a positive
-// activation below fp16's range becomes +0, not a floored subnormal): ONE v_med3 against -0 does ReLU, bound and mask (the median of
-// (v, -0, bound) is -0 for v < 0), the conversions keep the sign of zero, and a -0 operand adds nothing to any product sum (x + -0 = x,
-// and +0 + -0 = +0: the sums' bits do not change) -- where the floor took a compare, a v_med3 and a select per element in the forward's
-// epilogues and in the backward's recomputation of h0.  The backward reads the mask as "sign bit clear" (bf_pos).  A pre-activation that
-// is EXACTLY +0 gives hi = +0, i.e. counts as positive (its contribution is multiplied by h = 0 or is a ReLU derivative at the kink:
-// torch takes 0 there; this takes 1 -- measure zero for float inputs, documented in DESIGN section 4).
-#ifndef F8_SIGNMASK
-#define F8_SIGNMASK 1
-#endif
+// x' = 2^6 relu(v) saturated at fp16's largest value, from v' = 2^6 v: one v_med3 (ReLU and the bound together).
+__device__ __forceinline__ float bf_act(float vs) { return __builtin_amdgcn_fmed3f(vs, 0.f, 65504.0f); }
+// Where the hi plane of x' is going to be read as a ReLU mask, the mask travels in the SIGN of the hi part -- hi = -0 where v <= 0,
+// hi >= +0 where v > 0 (a positive activation below fp16's range becomes +0): ONE v_med3 against -0 does ReLU, bound and mask (the
+// median of (v, -0, bound) is -0 for v < 0), the conversions keep the sign of zero, and a -0 operand adds nothing to any product sum
+// (x + -0 = x, and +0 + -0 = +0: the sums' bits do not change).  The backward reads the mask as "sign bit clear" (bf_pos).  A
+// pre-activation that is EXACTLY +0 gives hi = +0, i.e. counts as positive (its contribution is multiplied by h = 0 or is a ReLU
+// derivative at the kink: torch takes 0 there; this takes 1 -- measure zero for float inputs, documented in DESIGN section 4).
+// Round 6 measured it against the earlier mask "hi > 0", which floored positive activations at fp16's smallest subnormal -- a compare,
+// a v_med3 and a select per element in the forward's epilogues and in the backward's recomputation of h0 (a compile-time knob, since
+// retired: profiles/r06_signmask_ab.txt).
 __device__ __forceinline__ float bf_act_s(float vs) { return __builtin_amdgcn_fmed3f(vs, -0.0f, 65504.0f); }
 __device__ __forceinline__ bool bf_pos(_Float16 hi) {
-#if F8_SIGNMASK
     return __builtin_amdgcn_classh(hi, 0x3c0);                       // +0, +subnormal, +normal, +inf: one v_cmp_class_f16, like the compare it replaces
-#else
-    return hi > (_Float16)0.f;
-#endif
 }
 // the split of such an x' (bf_split<true> without its bound and floor)
 __device__ __forceinline__ void bf_split_act(float x, _Float16 &hi, _Float16 &lo) {
@@ -281,7 +269,7 @@ __device__ __forceinline__ void f8_epilogue_v(const float (&z)[4], int g, _Float
                                                                          fmaxf(z[2] * (1.0f / BF_HS), 0.f), fmaxf(z[3] * (1.0f / BF_HS), 0.f));
     float y[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = bf_act<false>(z[e]);
+    for (int e = 0; e < 4; ++e) y[e] = bf_act(z[e]);
     unsigned hi[2], lo[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -309,7 +297,6 @@ __device__ __forceinline__ void f8_epilogue_v(const float (&z)[4], int g, _Float
 // first MFMA (no accumulator initialisation).
 struct F8Pair { float y[8]; unsigned hi[4], lo[4]; };
 #define F8_ACC_BOUND (65504.0f * BF_WS)          /* 2^12 z that saturates 2^6 relu(z) at fp16's largest value */
-#define F8_ACC_FLOOR (5.9604645e-8f * BF_WS)     /* ... and the one whose 2^6 relu(z) is fp16's smallest subnormal (MASKED: hi > 0 wherever z > 0) */
 //   planes (LDS): 2^6 h for the next layer;   rows: fp32 rows of h (the activation store of every backward but the fused one) or nullptr;
 //   img: the tile's PLANE IMAGE in HBM or nullptr -- the fused backward's LDS layout (two [64][128] fp16 planes hi | lo, 256-byte
 //   rows, bf_swz), which that kernel pulls into its region by LDS-DMA with nothing left to convert.
@@ -327,20 +314,14 @@ __device__ __forceinline__ void f8_epi_step(F8Pair &st, const f32x4v &a0, const 
         const int q2 = j / 6, i = j - 6 * q2, e = 4 * u + 2 * q2, q = 2 * u + q2;   // packed pair q = elements e, e + 1 of the state
         if (i < 2) {
             const float v = am[2 * q2 + i];
-#if F8_SIGNMASK
             st.y[e + i] = __builtin_amdgcn_fmed3f(v, MASKED ? -0.0f : 0.f, F8_ACC_BOUND);
-#else
-            st.y[e + i] = MASKED ? (v > 0.f ? __builtin_amdgcn_fmed3f(v, F8_ACC_FLOOR, F8_ACC_BOUND) : 0.f) : __builtin_amdgcn_fmed3f(v, 0.f, F8_ACC_BOUND);
-#endif
         }
-#if F8_SIGNMASK
         else if (i == 2 && MASKED) {                                 // scale, convert, pack -- keeping the sign of zero (v_fma_mix's + 0 would lose it)
             typedef float f32x2s __attribute__((ext_vector_type(2)));
             const f32x2s tv = {st.y[e] * (1.0f / BF_WS), st.y[e + 1] * (1.0f / BF_WS)};
             st.hi[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(tv, h16x2));
         }
         else if (i == 3 && MASKED) {}
-#endif
         else if (i == 2) bf_mix_hi<true, false>(st.hi[q], st.y[e], 1.0f / BF_WS);
         else if (i == 3) bf_mix_hi<true, true>(st.hi[q], st.y[e + 1], 1.0f / BF_WS);
         else if (i == 4) bf_mix_lo<true, false>(st.lo[q], st.y[e], 1.0f / BF_WS, st.hi[q]);
@@ -617,7 +598,7 @@ struct F9Layer0 {
     }
     __device__ __forceinline__ void step(int g, int k) {             // step k (0..12) of group g's epilogue
         const f32x4v &zz = z[g & 1];
-        if (k < 4) y[k] = bf_act<false>(zz[k]);
+        if (k < 4) y[k] = bf_act(zz[k]);
         else if (k < 8) { const int q = (k - 4) >> 1; if (k & 1) bf_mix_hi<false, true>(hi[q], y[2 * q + 1], 1.0f); else bf_mix_hi<false, false>(hi[q], y[2 * q], 1.0f); }
         else if (k < 12) { const int q = (k - 8) >> 1; if (k & 1) bf_mix_lo<false, true>(lo[q], y[2 * q + 1], 1.0f, hi[q]); else bf_mix_lo<false, false>(lo[q], y[2 * q], 1.0f, hi[q]); }
         else {
@@ -777,9 +758,8 @@ __device__ __forceinline__ void level_fwd9_body(const HeadCfg &hc, const LevelJo
     PT(9);
 }
 
-// The per-point warp of the bf16 forward (nets.py:119-135): one thread per point, from the saved head record -- the same
-// head_warp_fwd as the in-kernel warp of the default path, hence the same bits.
-// point p of pair b: head record -> warped point (rows: NDP_NHMAX floats of LDS private to the calling thread)
+// The per-point warp of the bf16 forward (nets.py:119-135), point p of pair b: head record -> warped point (rows: NDP_NHMAX floats of
+// LDS private to the calling thread)
 __device__ __forceinline__ void eng_warp_point(const ndp_engine &e, const ndp_pair_state &st, int b, int p, float *o) {
     const HeadCfg hc = make_head_cfg(desc_at_level(e.desc, st.level));
     const float *hr = e.heads + ((size_t)b * e.n_cap + p) * NDP_HROW;
@@ -793,21 +773,6 @@ __device__ __forceinline__ void eng_warp_point(const ndp_engine &e, const ndp_pa
     head_warp_fwd(hc, o, x, c, out);
     float *xo = pts + ((size_t)(st.cur ^ 1) * e.n_cap + p) * 3;
     xo[0] = out[0]; xo[1] = out[1]; xo[2] = out[2];
-}
-extern "C" __global__ void __launch_bounds__(256)
-k_eng_warp(ndp_engine e, int parity) {
-    __shared__ __attribute__((aligned(16))) float rows[256 * NDP_LROW];       // per-thread head rows (run-time row offsets; NDP_LROW: bank spread)
-    const int b = blockIdx.y, t = threadIdx.x;
-    // (level, buffer parity and geometry requested side by side and tested once: see eng_fwd8_stage)
-    const ndp_pair_state *stp = e.state + (size_t)parity * e.B + b;
-    ndp_pair_state st;
-    st.level = stp->level; st.cur = stp->cur;
-    const ndp_pair_geom gm = e.geom[b];
-    const int p = blockIdx.x * 256 + t;
-    if ((st.level >= e.m) | (st.cur < 0) | (gm.K + gm.S < 0)) return;
-    if (e.gmax && blockIdx.x == 0 && t == 0) e.gmax[b] = 0;          // this tick's max |dO| starts from zero (k_eng_loss raises it)
-    if (p >= gm.K + gm.S) return;
-    eng_warp_point(e, st, b, p, rows + t * NDP_LROW);
 }
 
 // the forward stage of one workgroup (blockIdx.x: first tile / tile step gridDim.x; blockIdx.y: pair)
@@ -843,13 +808,13 @@ __device__ __forceinline__ void eng_fwd8_stage(const ndp_engine &e, int parity, 
     else level_fwd8_body(hc, job, smb, keep_h0, h1_image);
 }
 
-// warp_here: a handful of resident pairs with ONE tile per workgroup -- the tile's 64 per-point warps run on threads 0..63 of the
-// workgroup that produced their head record instead of in a launch of their own (k_eng_warp: 4.7 us + a boundary of a 74 us tick at
-// batch 1; with 16 or 32 tiles per workgroup the warp is a serial 5.5k-cycle tail per tile and stays a launch)
-// warp_here == 2 (round 6, second half): the workgroup warps ALL the points of its tiles behind its tile loop, 512 threads at a time --
-// the head records of two sweeps (1024 points) are requested together into per-thread LDS rows (the tile regions are dead), then the
-// per-point chains run -- instead of a launch of its own behind the forward (k_eng_warp: 10.8 us + a kernel boundary of a 0.63 ms
-// tick at 256 pairs, 62 MB re-read from HBM: here the records come back from this CU's own stores).  Same eng_warp_point arithmetic.
+// The per-point warp rides in the forward launch.  A handful of resident pairs with ONE tile per workgroup: the tile's 64 per-point
+// warps run on threads 0..63 of the workgroup that produced their head record (round 4: a launch of its own cost 4.7 us + a boundary
+// of a 74 us tick at batch 1).  warp_tail (round 6, second half): the workgroup warps ALL the points of its tiles behind its tile loop,
+// 512 threads at a time -- the head records of two sweeps (1024 points) are requested together into per-thread LDS rows (the tile
+// regions are dead), then the per-point chains run.  The separate warp launch it replaced (kept as gemm_mode bit 512 until ABI
+// 204) took 10.8 us + a kernel boundary of a 0.63 ms tick at 256 pairs and re-read 62 MB from HBM: here the records come back
+// from this CU's own stores (profiles/r06_warp_tail_ab.txt).  Same eng_warp_point arithmetic.
 __device__ __forceinline__ void eng_warp_tail(const ndp_engine &e, int parity, unsigned char *smb) {
     __syncthreads();                                                 // the tiles' head records (this workgroup's own stores) are visible
     const int b = blockIdx.y, t = threadIdx.x;
@@ -892,12 +857,12 @@ __device__ __forceinline__ void eng_warp_tail(const ndp_engine &e, int parity, u
 }
 
 extern "C" __global__ void __launch_bounds__(512, 1)
-k_eng_fwd8(ndp_engine e, int parity, int warp_here) {
+k_eng_fwd8(ndp_engine e, int parity, int warp_tail) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
     PT_INIT;
     eng_fwd8_stage(e, parity, smb);
-    if (warp_here == 2) eng_warp_tail(e, parity, smb);
-    else if (warp_here) {
+    if (warp_tail) eng_warp_tail(e, parity, smb);
+    else {
         __syncthreads();                                             // the tile's head record (this workgroup's own stores) is visible
         const int b = blockIdx.y, t = threadIdx.x;
         const ndp_pair_state st = e.state[parity * e.B + b];

@@ -1025,10 +1025,10 @@ k_nn(const float *x, int S, const float *y, int T, float *d2x, int *idx_x, float
 }
 
 // Latency shape of the exact 1-NN (few pairs resident: one pair must spread over the chip).  A workgroup owns 64
-// queries, one per lane; its four waves each scan a quarter of every 2048-reference stage (LDS, broadcast reads, the
-// same packed arithmetic and sub-chunk bookkeeping as nn_body), then the four candidates of a query are folded in
-// reference order (strict <: the earliest quarter keeps ties).  S/64 + T/64 workgroups per pair instead of S/512 + T/512.
-template <int NW = 4>
+// queries, one per lane; its NW waves each scan an NW-th of every 2048-reference stage (LDS, broadcast reads, the
+// same packed arithmetic and sub-chunk bookkeeping as nn_body), then the NW candidates of a query are folded in
+// reference order (strict <: the earliest part keeps ties).  S/64 + T/64 workgroups per pair instead of S/512 + T/512.
+template <int NW>
 __device__ __forceinline__ void nn_lat_body(const float *q, int nq, const float *r, int nr, float *d2, int *idx,
                                             int qbase, float *sm /*[3][NN_STAGE] + [NW][64] + [NW][64]*/) {
     constexpr int NT = 64 * NW;                                     // threads of the workgroup: NW waves share the 64 queries
@@ -1127,7 +1127,6 @@ __device__ __forceinline__ void nn_lat_body(const float *q, int nq, const float 
         idx[i] = k;
     }
 }
-static constexpr int kSmemNnLatBytes = (3 * NN_STAGE + 512) * 4;
 
 // sum_i sqrt(d2_i) [d2_i < trunc], deterministic block reduction (all 256 threads get the value)
 __device__ __forceinline__ float l1_sum(const float *d2, int n, float trunc, float *scratch) {
@@ -1536,13 +1535,8 @@ __device__ __forceinline__ void eng_nn_lat_stage(const ndp_engine &e, int parity
         if (threadIdx.x < 64 && qb + (int)threadIdx.x >= gm.T && qb + (int)threadIdx.x < e.t_cap) iy[qb + threadIdx.x] = -1;
     }
 }
-extern "C" __global__ void __launch_bounds__(256)
-k_eng_nn_lat(ndp_engine e, int parity) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    eng_nn_lat_stage<4>(e, parity, sm);
-}
-// the same with eight waves per 64 queries (each scans an eighth of every stage): what the engine launches (round 4) -- at batch 1
-// the stage is one workgroup's latency, 10.7 -> us (the fold over the waves keeps the lowest index: same results)
+// eight waves per 64 queries (each scans an eighth of every stage): what the engine launches (round 4; four waves were measured and
+// retired as gemm_mode bit 128) -- at batch 1 the stage is one workgroup's latency (the fold over the waves keeps the lowest index)
 extern "C" __global__ void __launch_bounds__(512)
 k_eng_nn_lat8(ndp_engine e, int parity) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1600,7 +1594,7 @@ k_nn1_rows(int S, int T, int n_cap, const float *ws_row, float *d2x, int *idx_x)
 // Does the engine's nearest-neighbour stage run as k_eng_nn_mx8 (one workgroup and ONE row partial per 512 targets)?  The launcher and
 // the loss stage's fold of the row partials ask the same question.
 __host__ __device__ inline bool eng_nn_mx8(const ndp_engine &e) {
-    return e.w_cd != 0.f && e.t_cap > 0 && e.nn_mode == 2 && nn2_lds_floats(e.n_cap, 8) * 4 <= 160 * 1024 && !(e.gemm_mode & 128);
+    return e.w_cd != 0.f && e.t_cap > 0 && e.nn_mode == 2 && nn2_lds_floats(e.n_cap, 8) * 4 <= 160 * 1024;
 }
 
 // Loss, early-stop decision and dL/dx' for every pair (one launch per tick).
@@ -1616,8 +1610,7 @@ struct LossSmem {
     int order[LG_CHUNK];                                                  // targets grouped by their nearest source point
     __attribute__((aligned(16))) float rows[256 * NDP_LROW];              // per-thread head rows
 };
-// block reductions over the 256 ACTIVE threads of a workgroup (t: their index; the others only keep the barriers company -- the
-// persistent small-batch tick runs this stage on the lower half of its 512-thread workgroups)
+// block reductions over the 256 ACTIVE threads of a workgroup (t: their index; the others only keep the barriers company)
 __device__ __forceinline__ float block_sum_256_t(float v, float *scratch, int t, bool act) {
     if (act) scratch[t] = v;
     __syncthreads();
@@ -2082,7 +2075,6 @@ k_eng_update_rest(ndp_engine e, int parity) {
     eng_update_param(e, b, ns, desc_at_level(e.desc, ns.step_level), i);
 }
 
-#include "ndp_tick_small.inc"
 #include "ndp_generic.inc"
 
 // ------------------------------------------------------------------------------------------------
@@ -2390,7 +2382,7 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 #ifndef NDP_BUILD_ID
 #define NDP_BUILD_ID "unversioned"
 #endif
-extern "C" int ndp_version(void) { return 203; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written
+extern "C" int ndp_version(void) { return 204; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written; 204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }
@@ -2712,6 +2704,8 @@ static int engine_g8(const ndp_engine *e) { return (e->gemm_mode & 7) == 7 ? e->
 // stages [stage_lo, stage_hi] of every tick: 0 forward, 1 nearest neighbours, 2 loss / decision / dL/dx', 3 bwd2, 4 bwd1, 5 update
 static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipStream_t s, hipEvent_t *ev, int stage_lo = 0, int stage_hi = NDP_TICK_KERNELS - 1) {
     if (int rc = check_engine(e, "ndp_engine_run")) return rc;
+    if (e->gemm_mode & ~(1 | 2 | 4 | 8 | 16 | 32 | 1024))
+        return fail(NDP_E_INVALID, "ndp_engine_run: gemm_mode is a mask of 1 (forward), 2 (bwd1), 4 (bwd2) on fp16 splits, 8 (the split forward keeps h0), 16 (bwd2 and bwd1 as two launches), 32 (the fused backward also writes dz1), 1024 (the whole Adam step in k_eng_update) (see ndp_hip.h)");
     const bool nn = e->w_cd != 0.f && e->t_cap > 0;
     if (nn && (!e->nn_row || !e->d2x || !e->d2y || !e->idx_x || !e->idx_y || !e->tgt))
         return fail(NDP_E_INVALID, "ndp_engine_run: Chamfer term without nearest-neighbour buffers");
@@ -2734,14 +2728,13 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         if (int rc = set_smem((const void *)k_eng_nn_mx, nn2_lds_floats(e->n_cap) * 4)) return rc;
         if (nn2_lds_floats(e->n_cap, 8) * 4 <= 160 * 1024) if (int rc = set_smem((const void *)k_eng_nn_mx8, nn2_lds_floats(e->n_cap, 8) * 4)) return rc;
     }
-    // the matrix-pipe kernel in its 8-wave shape (512 targets per workgroup) unless gemm_mode bit 128 asks for the 4-wave one (A/B)
+    // the matrix-pipe kernel in its 8-wave shape (512 targets per workgroup) where its LDS table fits
     const bool nn_mx8 = eng_nn_mx8(*e);
     const dim3 blk(256);
     const dim3 g_lvl(e->G, e->B);
     // bf16 kernels: one 8-wave workgroup per CU.  With all three of them on (mask 7) the engine is sized for that (G workgroups and G
     // partials per pair); in a mixed configuration they take half the fp32 grid and zero the partials they do not write.
     const dim3 g_fwd8(engine_g8(e), e->B);
-    if (e->gemm_mode < 0 || e->gemm_mode > 2047) return fail(NDP_E_INVALID, "ndp_engine_run: gemm_mode is a mask of 1 (forward), 2 (bwd1), 4 (bwd2) on fp16 splits, 8 (the split forward keeps h0), 16 (bwd2 and bwd1 as two launches), 32 (the fused backward also writes dz1), 64 (the Adam step inside the fused backward), 128 / 256 / 512 / 1024 (see ndp_hip.h)");
     // both backward layers on the splits: ONE launch (k_eng_bwd_f, stage 3; stage 4 launches nothing) unless bit 16 asks for the two round-3 kernels
     // width / depth other than 128 / 3: the generic fp32 level kernels (csrc/ndp_generic.inc); gemm_mode selects nothing there
     const bool generic = gen_is_generic(e->desc);
@@ -2758,47 +2751,9 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
     const dim3 g_nn_lat(e->n_cap / 64 + e->t_cap / 64, e->B);
     const dim3 g_upd((e->P + 255) / 256, e->B);
     const dim3 g_loss((e->n_cap + 255) / 256 + 1, e->B);   // + 1: the loss / decision workgroup
-    // MEASURED VARIANT (gemm_mode bit 256, round 4): a handful of resident pairs run the whole chunk of ticks as ONE persistent launch whose
-    // stages are separated by pair barriers (csrc/ndp_tick_small.inc) -- bitwise the launches, but 115 us per tick against 74 at batch 1:
-    // five agent-scope release / acquire pairs per tick (the per-XCD L2s are not coherent: every release writes an L2 back) cost more
-    // than six kernel boundaries.  Needs: fused split backward, latency-shape NN, one tile per workgroup, every workgroup resident.
-    // one tile per level-kernel workgroup and few of them: the per-point warp rides in the forward launch (ndp_fwd_split.inc)
+    // one tile per level-kernel workgroup and few of them: the per-point warp rides in the forward launch (ndp_fwd_split.inc); everything
+    // else on the split forward: the workgroup warps its tiles' points behind its tile loop (eng_warp_tail)
     const bool warp_in_fwd = (e->gemm_mode & 1) && (int)g_fwd8.x == e->n_cap / NDP_TILE && e->B * (int)g_fwd8.x <= 256;
-    // everything else on the split forward: the workgroup warps its tiles' points behind its tile loop (eng_warp_tail); bit 512 of
-    // gemm_mode keeps the separate k_eng_warp launch (A/B, tests)
-#ifndef NDP_WARP_TAIL
-#define NDP_WARP_TAIL 1
-#endif
-    const bool warp_tail = NDP_WARP_TAIL && (e->gemm_mode & 1) && !warp_in_fwd && !(e->gemm_mode & 512);
-    const bool persistent = !ev && stage_lo == 0 && stage_hi == NDP_TICK_KERNELS - 1 && bwd_fused && (e->gemm_mode & 1) &&
-                            (e->gemm_mode & 256) && !(e->gemm_mode & (32 | 64)) && (!nn || e->nn_mode == 1) && e->G == e->n_cap / NDP_TILE &&
-                            e->B * e->G <= 256 && n_ticks > 0;
-    // its pair barriers spin: every one of the B x G workgroups has to be RESIDENT (512 threads and ~147 KB of LDS each: one per CU).  The
-    // occupancy query x the device's CU count has to cover the grid, else the per-stage launches below run instead; a second stream
-    // that holds CUs (bench.py's two engines) can still delay residency -- the variant is for an engine that has the device to itself.
-    bool persistent_fits = false;
-    if (persistent) {
-        if (int rc = set_smem((const void *)k_eng_tick_small, kSmemTickSmallBytes)) return rc;
-        // (resident workgroups the device holds: queried once per device -- this is the batch-1 latency path, three HIP calls per
-        //  ndp_engine_run were host time on it)
-        static long long s_resident[64];                             // 0: not queried yet; -1: the query failed
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-            if (s_resident[dev] == 0) {
-                int per_cu = 0, cus = 0;
-                s_resident[dev] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_eng_tick_small, 512, kSmemTickSmallBytes) == hipSuccess &&
-                                   hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0)
-                                      ? (long long)per_cu * cus : -1;
-            }
-            persistent_fits = s_resident[dev] >= (long long)e->B * e->G;
-        }
-    }
-    if (persistent && persistent_fits) {
-        HIP_TRY(hipMemsetAsync(e->gmax + e->B, 0, sizeof(unsigned) * e->B, s), "pair barrier counters");
-        hipLaunchKernelGGL(k_eng_tick_small, dim3(e->G, e->B), dim3(512), kSmemTickSmallBytes, s, *e, tick0, n_ticks);
-        HIP_TRY(hipGetLastError(), "persistent tick launch");
-        return 0;
-    }
     for (int k = 0; k < n_ticks; ++k) {
         const int parity = (tick0 + k) & 1;
         hipEvent_t *q = ev ? ev + (size_t)k * (NDP_TICK_KERNELS + 1) : nullptr;
@@ -2808,16 +2763,12 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         NDP_EV();
         if (!NDP_ST(0)) {}
         else if (generic) hipLaunchKernelGGL(k_eng_fwd_gen, g_lvl, blk, gen_fwd_floats(e->desc.width) * 4, s, *e, parity);
-        else if (e->gemm_mode & 1) {
-            hipLaunchKernelGGL(k_eng_fwd8, g_fwd8, dim3(512), kSmemFwd8Bytes, s, *e, parity, warp_in_fwd ? 1 : (warp_tail ? 2 : 0));
-            if (!warp_in_fwd && !warp_tail) hipLaunchKernelGGL(k_eng_warp, dim3((e->n_cap + 255) / 256, e->B), blk, 0, s, *e, parity);
-        }
+        else if (e->gemm_mode & 1) hipLaunchKernelGGL(k_eng_fwd8, g_fwd8, dim3(512), kSmemFwd8Bytes, s, *e, parity, warp_in_fwd ? 0 : 1);
         else hipLaunchKernelGGL(k_eng_fwd, g_lvl, blk, kSmemFwdBytes, s, *e, parity);
         NDP_EV();
         if (!NDP_ST(1)) {}
-        else if (nn && e->nn_mode == 1 && !(e->gemm_mode & 128) && e->B <= 2) hipLaunchKernelGGL(k_eng_nn_lat16, g_nn_lat, dim3(1024), (3 * NN_STAGE + 2 * 1024) * 4, s, *e, parity);
-        else if (nn && e->nn_mode == 1 && !(e->gemm_mode & 128)) hipLaunchKernelGGL(k_eng_nn_lat8, g_nn_lat, dim3(512), (3 * NN_STAGE + 2 * 512) * 4, s, *e, parity);
-        else if (nn && e->nn_mode == 1) hipLaunchKernelGGL(k_eng_nn_lat, g_nn_lat, blk, kSmemNnLatBytes, s, *e, parity);
+        else if (nn && e->nn_mode == 1 && e->B <= 2) hipLaunchKernelGGL(k_eng_nn_lat16, g_nn_lat, dim3(1024), (3 * NN_STAGE + 2 * 1024) * 4, s, *e, parity);
+        else if (nn && e->nn_mode == 1) hipLaunchKernelGGL(k_eng_nn_lat8, g_nn_lat, dim3(512), (3 * NN_STAGE + 2 * 512) * 4, s, *e, parity);
         else if (nn_mx8) hipLaunchKernelGGL(k_eng_nn_mx8, dim3((e->t_cap + 511) / 512, e->B), dim3(512), nn2_lds_floats(e->n_cap, 8) * 4, s, *e, parity);
         else if (nn && e->nn_mode == 2) hipLaunchKernelGGL(k_eng_nn_mx, g_nn, blk, nn2_lds_floats(e->n_cap) * 4, s, *e, parity);
         else if (nn) hipLaunchKernelGGL(k_eng_nn, g_nn, blk, nn_lds, s, *e, parity, stage_x);
@@ -2834,7 +2785,7 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         else if (e->gemm_mode & 2) hipLaunchKernelGGL(k_eng_bwd1_8, g_fwd8, dim3(512), kSmemBwd18Bytes, s, *e, parity);
         else hipLaunchKernelGGL(k_eng_bwd1, g_lvl, blk, kSmemBwdBytes, s, *e, parity);
         NDP_EV();
-        if (!NDP_ST(5) || (bwd_fused && (e->gemm_mode & 64))) {}
+        if (!NDP_ST(5)) {}
         else if (bwd_fused && bf_adam_in_tail(*e)) hipLaunchKernelGGL(k_eng_update_rest, dim3((upd_rest_count(e->P) + 255) / 256, e->B), blk, 0, s, *e, parity);
         else hipLaunchKernelGGL(k_eng_update, g_upd, blk, 0, s, *e, parity);
         NDP_EV();

@@ -47,6 +47,8 @@ class OptConfig:
 #   nn matrix : the one-pass NN with the distances on the bf16 matrix pipe and exact re-evaluation (bit-identical results).
 DEFAULT_GEMM_MODE = 7
 DEFAULT_NN_MATRIX = True
+# every bit gemm_mode may carry (ndp_hip.h); bits 64, 128, 256 and 512 selected measured variants until ABI 204 and are refused
+GEMM_MODE_BITS = 1 | 2 | 4 | 8 | 16 | 32 | 1024
 
 
 def resolve_modes(B, n_cap, t_cap, gemm_mode=None, nn_mode=None, nn_matrix=None):
@@ -57,9 +59,10 @@ def resolve_modes(B, n_cap, t_cap, gemm_mode=None, nn_mode=None, nn_matrix=None)
     if gemm_mode is None:
         gemm_mode = DEFAULT_GEMM_MODE
     gemm_mode = int(gemm_mode)
-    if not 0 <= gemm_mode <= 2047:
+    if gemm_mode & ~GEMM_MODE_BITS:
         raise N.NdpError(f"gemm_mode must be a mask of 1 (forward) | 2 (bwd1) | 4 (bwd2) [| 8: the split forward also stores h0 | 16: "
-                         f"the split backward as two launches | 32: the fused backward also writes dz1 -- tests | 64: the Adam step inside the fused backward | 256: persistent small-batch tick | 512: the per-point warp as a launch of its own | 1024: at G = 1 the Adam step of the two 128 x 128 matrices behind the fused backward's tile loop], got {gemm_mode}")
+                         f"the split backward as two launches | 32: the fused backward also writes dz1 -- tests | 1024: the whole Adam "
+                         f"step in the update stage], got {gemm_mode}")
     fits2 = bool(lib.ndp_engine_nn_matrix_fits(n_cap))
     fits0 = bool(lib.ndp_engine_nn_onepass_fits(n_cap))
     if nn_mode is not None:
@@ -144,7 +147,7 @@ class BatchedEngine:
         self.state_nbytes = ctypes.sizeof(N.PairState)
         self.state = torch.zeros(2, B, self.state_nbytes, device=d, dtype=torch.uint8)
         self.geom = torch.zeros(B, 4, device=d, dtype=torch.int32)
-        self.gmax = torch.zeros(2 * B, device=d, dtype=torch.int32)  # [0, B): max |dO| per pair and tick, the split backward's gradient scale; [B, 2B): tickets of gemm_mode bit 64
+        self.gmax = torch.zeros(B, device=d, dtype=torch.int32)      # max |dO| per pair and tick: the split backward's gradient scale
         self._geom_h = np.zeros((B, 4), dtype=np.int32)
         self._state_h = torch.zeros(B, self.state_nbytes, dtype=torch.uint8).pin_memory()
         self._snap = [torch.zeros(B, self.state_nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]

@@ -275,16 +275,12 @@ typedef struct ndp_engine {
                                         csrc/ndp_bwd_fused.inc: dz1 stays in LDS, one accumulator per product on operands pre-scaled
                                         by powers of two -- activations and weights beyond 1023 saturate there); bit 16: as the two
                                         launches k_eng_bwd2_8 + k_eng_bwd1_8 instead; bit 32 (tests): the fused launch also writes
-                                        dz1 over the h2 plane of `act`, where the two-launch form leaves it.
-                                        Measured variants kept behind bits: 64 the Adam step by the last-arriving
-                                        backward workgroup of a pair (no k_eng_update launch; gmax must then be [2 B]); 128 the 4-wave
-                                        shapes of the nearest-neighbour kernels; 256 a persistent one-launch tick for a handful of
-                                        resident pairs (k_eng_tick_small; gmax [2 B]) -- all bitwise the default, all slower;
-                                        512 the per-point warp of the split forward as a launch of its own (k_eng_warp) instead of
-                                        behind the forward workgroup's tile loop (same arithmetic, same bits); 1024 the whole Adam
+                                        dz1 over the h2 plane of `act`, where the two-launch form leaves it.  1024: the whole Adam
                                         step in k_eng_update -- without it an engine with G == 1 steps the two 128 x 128 matrices
                                         behind the fused backward's tile loop (no gradient partial of them is written: gpart's two
                                         matrix blocks are then undefined) and the rest in k_eng_update_rest: bitwise the same state.
+                                        No other bit is accepted (ABI 204: bits 64, 128, 256 and 512 selected measured variants,
+                                        DESIGN.md section 0, and are refused).
                                         nn_mode 0: one-pass kernel, distances on the vector pipe; 2: the same on the bf16 matrix pipe
                                         with exact re-evaluation (bit-identical, needs ndp_engine_nn_matrix_fits(n_cap)); 1: latency
                                         shape -- two passes in 64-query workgroups, S/64 + T/64 of them per pair -- for a handful of

@@ -41,6 +41,18 @@ def test_struct_layouts_match_the_header():
     assert int(re.search(r"#define NDP_MAX_LOAD_JOBS (\d+)", header).group(1)) == _native.MAX_LOAD_JOBS
 
 
+def test_resolve_modes_refuses_the_retired_gemm_mode_bits():
+    """Bits 64, 128, 256 and 512 of gemm_mode selected measured variants until ABI 204: asking for one fails instead of quietly
+    running the default, and every live bit still resolves."""
+    from deformationpyramid_amd import _native
+    from deformationpyramid_amd.engine import resolve_modes
+    for bit in (64, 128, 256, 512):
+        with pytest.raises(_native.NdpError, match="gemm_mode must be a mask"):
+            resolve_modes(256, 2048, 2048, gemm_mode=7 | bit)
+    for mode in (0, 7, 7 | 8, 7 | 16, 7 | 32, 7 | 1024):
+        assert resolve_modes(256, 2048, 2048, gemm_mode=mode)[0] == mode
+
+
 def test_the_package_reads_no_environment_variable_and_variants_are_explicit():
     """Nothing under deformationpyramid_amd/ reads the environment (the one WRITE is GPU_MAX_HW_QUEUES' default, before HIP starts): an
     experiment build of the library can only be selected by _native.use_variant() -- which the measurement tools call for

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libndp_hip.so with extra -D flags next to the product library (same flags as deformationpyramid_amd/_native.py):
-#   bash tools/experiments/build_variant.sh tools/experiments/var/lib4w.so -DNDP_EXPERIMENT_FWD_4W
+#   bash tools/experiments/build_variant.sh tools/experiments/var/hrow136.so -DB8_HROW=136
 # and run anything against it with NDP_HIP_LIB=<that file>.
 R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$1; shift

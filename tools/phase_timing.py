@@ -99,10 +99,9 @@ for lo, n, tag in ((36, wg_grad, "loss gradient workgroup"), (48, wg_dec, "loss 
 if eng.nn_mode == 2:
     nmn = ["setup: targets + B operands, sources -> LDS, |x|max", "A operands of a 128-source block (x4 per wave)", "distances: 8 tiles x (8 MFMA + row / column minima)",
            "rows: transposition, best class, exact evaluation", "barrier (waves done with their blocks)", "columns: fold table, exact re-scan of the winning block"]
-    mx8 = not (eng.gemm_mode & 128)                          # the 8-wave shape: 512 targets per workgroup
-    wgs = B * ((eng.t_cap + (511 if mx8 else 255)) // (512 if mx8 else 256)) * ticks
+    wgs = B * ((eng.t_cap + 511) // 512) * ticks               # the 8-wave shape: 512 targets per workgroup
     tot = sum(buf[64 + i] for i in range(6))
-    print(f"nn_mx{'8' if mx8 else ''}: {tot / wgs:.0f} cycles per workgroup (all sources x {512 if mx8 else 256} targets; thread 0 wall)")
+    print(f"nn_mx8: {tot / wgs:.0f} cycles per workgroup (all sources x 512 targets; thread 0 wall)")
     for i, nm in enumerate(nmn):
         print(f"   {nm:58s} {buf[64 + i] / wgs:9.0f}  {100.0 * buf[64 + i] / max(tot, 1):5.1f} %")
 FUSED = (eng.gemm_mode & 7) == 7 and not (eng.gemm_mode & 16)
@@ -134,24 +133,9 @@ if False:
     print(f"bwd1_8: {tot / tiles:.0f} cycles per tile (thread 0 wall)")
     for i, nm in enumerate(nm1):
         print(f"   {nm:52s} {buf[24 + i] / tiles:9.0f}  {100.0 * buf[24 + i] / max(tot, 1):5.1f} %")
-if getattr(eng, 'fwd_as', False):
-    f9 = ["stage W1 / W0 (once per workgroup)", "x, sincos, layer-0 operands", "layer 0 (12 MFMA) + h0 store + split", "layer 1 (192 MFMA) + h1 store",
-          "phase barrier", "stage W2 / Wh (once per workgroup)", "h1 read back + split", "layer 2 + heads (240 MFMA) + h2 store", "-", "-", "-"]
-    tot = sum(buf[12 + i] for i in range(11))
-    print(f"fwd_as (activation-stationary): {tot / tiles:.0f} cycles per 64 points (wave 0 wall; a wave's 32-point group = 1/4 of the workgroup's work per 64 points... see below)")
-    for i, nm in enumerate(f9):
-        print(f"   {nm:48s} {buf[12 + i] / tiles:9.0f}  {100.0 * buf[12 + i] / max(tot, 1):5.1f} %")
-elif eng.gemm_mode & 1:
+if eng.gemm_mode & 1:
     f8 = ["-", "layer 0 (two MFMAs per group) + split + planes", "barrier", "-", "layer 1 MFMA + epilogue", "barrier", "-",
           "layer 2 MFMA + epilogue", "barrier", "heads (waves 0..3)", "weights -> registers (once per workgroup; 4-wave experiment only)"]
-    if "-DNDP_EXPERIMENT_FWD_4W" in extra:
-        f8 = ["-", "P0: layer 0, epilogue (L0, g0) [+ heads of the previous tile's g1]", "barriers (six per tile)", "P1: MFMAs (L1, g0) | epilogue (L0, g1)",
-              "P2: MFMAs (L1, g1) | epilogue (L1, g0)", "P3: MFMAs (L2, g0) | epilogue (L1, g1)", "P4: MFMAs (L2, g1) | epilogue (L2, g0)",
-              "P5: epilogue (L2, g1), heads of g0", "-", "-", "weights -> registers (once per workgroup)"]
-    if "-DNDP_EXPERIMENT_FWD_LP" in extra:
-        f8 = ["-", "H1: L1 waves MFMAs (L1, s) | L2 waves heads (s-3)", "barrier", "H2, L1 waves: epilogue (L1, s)",
-              "H2: L1 waves encode s+2 | L2 waves MFMAs (L2, s-1)", "barrier", "H2, L1 waves: layer 0 of s+1", "H1, L2 waves: epilogue (L2, s-2)", "-", "-",
-              "weights -> registers, first encodings (once per workgroup)"]
     tot = sum(buf[12 + i] for i in range(11))
     print(f"fwd8 (fp16 splits): {tot / tiles:.0f} cycles per tile (thread 0 wall)")
     for i, nm in enumerate(f8):

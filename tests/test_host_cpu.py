@@ -488,3 +488,168 @@ def test_native_pair_init_replays_torch_randperm_and_leaves_the_generator_where_
     assert torch.equal(st, after)
     torch.set_rng_state(st)
     assert torch.equal(torch.rand(4), follow)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The pair producer of register_batch (deformationpyramid_amd/batch.py) with a `prepare` that needs no device
+
+JOIN_S = 30.0                                         # a guard against a hang, not a measurement
+
+
+def _threads_ended(producer):
+    for th in producer.threads:
+        th.join(JOIN_S)
+    return not any(th.is_alive() for th in producer.threads)
+
+
+@pytest.mark.parametrize("W", [1, 3, 4])
+def test_pair_producer_delivers_in_index_order_whatever_finishes_first(W):
+    """50 items whose preparation finishes out of order (later items of a round sleep less): next() yields 0..49 in order, then
+    None, and item i was prepared by worker i % W, on a thread of the producer."""
+    import threading
+    import time
+    from deformationpyramid_amd.batch import PairProducer
+    finished = []
+
+    def prepare(item, rng_state, worker):
+        time.sleep(0.001 * (5 - item % 6))
+        finished.append(item)
+        return item, rng_state, worker, threading.current_thread()
+
+    torch.manual_seed(0)
+    prod = PairProducer(list(range(50)), prepare, workers=W, resident=4, draws=lambda item: 7)
+    assert len(prod.threads) == W + 1
+    got = [prod.next() for _ in range(50)]
+    assert prod.next() is None and prod.next(block=False) is None
+    prod.close()
+    assert _threads_ended(prod)
+    assert [i for i, _ in got] == list(range(50)) and [p[0] for _, p in got] == list(range(50))
+    assert all(p[2] == i % W and p[3] is prod.threads[1 + i % W] for i, p in got)
+    assert W == 1 or finished != sorted(finished)     # (the preparations did overtake each other)
+    # no draw counts (the torch-call replay consumes the global generator): ONE worker whatever `workers`, no state handed out
+    prod = PairProducer(list(range(20)), prepare, workers=W, resident=4)
+    got = [prod.next() for _ in range(20)]
+    assert prod.next() is None
+    prod.close()
+    assert _threads_ended(prod) and len(prod.threads) == 2
+    assert [i for i, _ in got] == list(range(20)) and all(p[1] is None and p[2] == 0 for _, p in got)
+
+
+def test_pair_producer_walks_the_generator_like_sequential_register_calls():
+    """Native replay: the state handed to item i is the seeded state skipped over the draws of items 0..i-1 one after the
+    other, and the global generator ends where the fully skipped one is -- with the draw counts of real pairs."""
+    from deformationpyramid_amd import _native as N
+    from deformationpyramid_amd.batch import PairProducer
+    from deformationpyramid_amd.config import load_config
+    from deformationpyramid_amd.nets import _native_rng_ok
+    from deformationpyramid_amd.registration import Registration
+    assert _native_rng_ok()
+    reg = Registration(load_config(os.path.join(ROOT, "config", "NDP.yaml"), device="cpu"))
+    shapes = [(8192, 8192), (1, 5), (2001, 777), (24856, 24856), (300, 300), (8192, 4000), (1500, 1564)]
+    draws = [reg._pair_draws(*s) for s in shapes]
+    assert len(set(draws)) > 3 and min(draws) > 0
+    L = N.host_lib()
+    torch.manual_seed(11)
+    st = torch.get_rng_state().clone()
+    want = []
+    for d in draws:
+        want.append(st.clone())
+        assert L.ndp_rng_skip(ctypes.c_void_p(st.data_ptr()), st.numel(), d) == 0
+    assert not torch.equal(st, want[0])
+    torch.manual_seed(11)
+    prod = PairProducer(shapes, lambda item, rng_state, worker: rng_state, workers=3, resident=4, draws=lambda item: reg._pair_draws(*item))
+    got = [prod.next() for _ in shapes]
+    assert prod.next() is None
+    prod.close()
+    for (i, state), w in zip(got, want):
+        assert torch.equal(state, w), i
+    assert torch.equal(torch.get_rng_state(), st)
+
+
+def test_pair_producer_raises_a_workers_exception_in_the_consumer_and_closes():
+    """prepare raises on item k: the items before it arrive, then next() raises that exception; close(failed=True) returns
+    with every thread ended (the other workers were blocked on their full queues by then)."""
+    from deformationpyramid_amd.batch import PairProducer
+    k, boom = 7, RuntimeError("item 7 cannot be prepared")
+
+    def prepare(item, rng_state, worker):
+        if item == k:
+            raise boom
+        return item
+
+    prod = PairProducer(list(range(2000)), prepare, workers=3, resident=4, draws=lambda item: 1)
+    assert [prod.next() for _ in range(k)] == [(i, i) for i in range(k)]
+    with pytest.raises(RuntimeError) as err:
+        prod.next()
+    assert err.value is boom
+    prod.close(failed=True)
+    assert _threads_ended(prod)
+
+    def draws(item):                                  # the stepping thread fails: the same route
+        raise boom
+    prod = PairProducer(list(range(2000)), prepare, workers=3, resident=4, draws=draws)
+    with pytest.raises(RuntimeError):
+        for _ in range(3):
+            prod.next()
+    prod.close(failed=True)
+    assert _threads_ended(prod)
+
+
+def test_pair_producer_closes_under_full_queues_when_the_consumer_gives_up():
+    """The consumer stops after two of 5000 items (queue depth 4 + 8): every producer thread is blocked on a full queue;
+    close(failed=True) returns and they have all ended."""
+    import time
+    from deformationpyramid_amd.batch import PairProducer
+    prod = PairProducer(list(range(5000)), lambda item, rng_state, worker: item, workers=3, resident=4, draws=lambda item: 1)
+    assert prod.next() == (0, 0) and prod.next() == (1, 1)
+    deadline = time.monotonic() + JOIN_S
+    while not all(q.full() for q in prod.out_q + prod.in_q) and time.monotonic() < deadline:
+        time.sleep(0.01)
+    assert all(q.full() for q in prod.out_q + prod.in_q) and all(th.is_alive() for th in prod.threads)
+    prod.close(failed=True)
+    assert _threads_ended(prod)
+
+
+def test_pair_producer_nonblocking_next_does_not_advance():
+    """Item 1's preparation is held by an Event: next(block=False) answers NOT_READY and stays on item 1 (although item 2, on
+    another worker, is ready); once released, a blocking next() returns item 1."""
+    import threading
+    from deformationpyramid_amd.batch import _NOT_READY, PairProducer
+    gate = threading.Event()
+
+    def prepare(item, rng_state, worker):
+        if item == 1:
+            assert gate.wait(JOIN_S)
+        return item
+
+    prod = PairProducer(list(range(6)), prepare, workers=3, resident=4, draws=lambda item: 1)
+    try:
+        assert prod.next() == (0, 0)
+        assert prod.next(block=False) is _NOT_READY and prod.next(block=False) is _NOT_READY
+        assert prod.cursor == 1
+        gate.set()
+        assert prod.next() == (1, 1)
+        assert [prod.next() for _ in range(4)] == [(i, i) for i in range(2, 6)] and prod.next() is None
+    finally:
+        gate.set()
+        prod.close(failed=True)
+    assert _threads_ended(prod)
+
+
+def test_pair_producer_without_prefetch_prepares_in_line():
+    """prefetch=False: no thread; prepare runs on the calling thread, when next() is called, with no generator state and no worker."""
+    import threading
+    from deformationpyramid_amd.batch import PairProducer
+    calls = []
+
+    def prepare(item, rng_state, worker):
+        calls.append((item, rng_state, worker, threading.current_thread()))
+        return item * 10
+
+    before = threading.active_count()
+    prod = PairProducer([1, 2, 3], prepare, workers=3, resident=4, draws=lambda item: 1, prefetch=False)
+    assert prod.threads == [] and threading.active_count() == before and calls == []
+    assert prod.next() == (0, 10) and len(calls) == 1
+    assert prod.next(block=False) == (1, 20) and prod.next() == (2, 30) and prod.next() is None
+    prod.close()
+    assert calls == [(i, None, None, threading.current_thread()) for i in (1, 2, 3)]

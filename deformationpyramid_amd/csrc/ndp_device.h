@@ -298,8 +298,11 @@ __device__ __forceinline__ void head_warp_fwd(const HeadCfg &hc, const float *o,
 
 // g = dL/dout -> d_o = dL/d(scaled head outputs).  d_o points at NDP_NHMAX floats in LDS (rows are
 // addressed with run-time offsets, which registers cannot do); unused rows are zeroed.
+// direct (may be nullptr): the three components of dL/dx that do NOT pass through the network -- the warp applied to x
+// with the head outputs held fixed: (1 - nr) g + s R^T (nr g)  (no gate: s R^T g ; sflow: the identity in place of s R^T).
+// The part through the positional encoding is added by the level backward (bwd1_body / gen_level_bwd_body, DX).
 __device__ __forceinline__ void head_warp_bwd(const HeadCfg &hc, const float *x, const PointHead &c,
-                                              const float *g_in, float g_nr, float *d_o) {
+                                              const float *g_in, float g_nr, float *d_o, float *direct = nullptr) {
     // the 6D backward needs the raw rot outputs: read them before the row is reused for the gradient
     float rraw[6];
 #pragma unroll
@@ -317,7 +320,17 @@ __device__ __forceinline__ void head_warp_bwd(const HeadCfg &hc, const float *x,
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) d_o[hc.row_trn + a] = g[a];
-    if (hc.motion == NDP_MOTION_SFLOW) return;
+    if (direct) {                                     // the gate's own path x -> out (nets.py:134); g is nr * g_in from here on
+#pragma unroll
+        for (int a = 0; a < 3; ++a) direct[a] = hc.nonrig ? (1.0f - c.nr) * g_in[a] : 0.f;
+    }
+    if (hc.motion == NDP_MOTION_SFLOW) {
+        if (direct) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) direct[a] += g[a];
+        }
+        return;
+    }
     float grx[3] = {g[0], g[1], g[2]};
     if (hc.motion == NDP_MOTION_SIM3) {
         float ds = 0.f;
@@ -332,6 +345,15 @@ __device__ __forceinline__ void head_warp_bwd(const HeadCfg &hc, const float *x,
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) G[a * 3 + b] = grx[a] * x[b];
+    if (direct) {                                     // (s R)^T g
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            float s = c.R[b] * grx[0];
+            s = fmaf(c.R[3 + b], grx[1], s);
+            s = fmaf(c.R[6 + b], grx[2], s);
+            direct[b] += s;
+        }
+    }
     float dr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     rot_bwd(hc.rotfmt, rraw, c, G, dr);
 #pragma unroll
@@ -359,7 +381,8 @@ __device__ __forceinline__ float block_sum_256(float v, float *scratch /* >= 256
 // lds_row: NDP_NHMAX floats of LDS private to the calling thread (run-time row offsets live there).
 __device__ __forceinline__ void point_head_bwd(const HeadCfg &hc, const float *heads_row /*global, NDP_HROW*/,
                                                const float *x, const float *g, float g_nr, float *lds_row,
-                                               float *dO_row /*global*/, float *amax = nullptr /* max |dO| of the row */) {
+                                               float *dO_row /*global*/, float *amax = nullptr /* max |dO| of the row */,
+                                               float *direct = nullptr /* 3 floats: see head_warp_bwd */) {
     if (heads_row) {                                 // (nullptr: the caller has already brought the row into lds_row)
 #pragma unroll
         for (int j = 0; j < NDP_NHMAX; j += 4)
@@ -368,7 +391,7 @@ __device__ __forceinline__ void point_head_bwd(const HeadCfg &hc, const float *h
     PointHead c;
     float out[3];
     head_warp_fwd(hc, lds_row, x, c, out);
-    head_warp_bwd(hc, x, c, g, g_nr, lds_row);
+    head_warp_bwd(hc, x, c, g, g_nr, lds_row, direct);
 #pragma unroll
     for (int j = 0; j < NDP_NHMAX; j += 4) {
         float4 v = *reinterpret_cast<const float4 *>(lds_row + j);

@@ -273,7 +273,12 @@ __device__ __forceinline__ void gen_wgrad(const float *z /*[o][GEN_PS]*/, const 
 
 // the backward of a workgroup's tiles: job.act = [n_hidden + 1][plane][W] as the forward left it, job.dO = [plane][16] from the head
 // backward (k_head_bwd / k_eng_loss: mlp_scale * dL/d(scaled head outputs), zero rows beyond n), job.gpart = this workgroup's partial
-__device__ __forceinline__ void gen_level_bwd_body(const HeadCfg &hc, const ndp_layer_desc &d, const BwdJob &job, float *sm) {
+// DX (ndp_level_bwd with dx; the engine's samples are detached): behind the layer-0 block, from D = dz0 and the saved encodings,
+//   dx[p][k] += freq (pe[2k+1][p] dpe[p][2k] - pe[2k][p] dpe[p][2k+1]),  dpe[p][c] = sum_o dz0[o][p] W0[o][c]  (o ascending)
+// on top of the direct term k_head_bwd_dx left there: one thread per point and axis, the tile's one workgroup -- no atomics.
+template <bool DX = false>
+__device__ __forceinline__ void gen_level_bwd_body(const HeadCfg &hc, const ndp_layer_desc &d, const BwdJob &job, float *sm,
+                                                   float *dx = nullptr, float freq = 0.f) {
     const int t = threadIdx.x, W = d.width, nhid = d.n_hidden, NH = hc.nh;
     float *D = sm, *I = sm + gen_buf(W), *dOs = sm + gen_bwd_do(W), *pes = sm + gen_bwd_pe(W);
     float *gp = job.gpart;
@@ -316,6 +321,18 @@ __device__ __forceinline__ void gen_level_bwd_body(const HeadCfg &hc, const ndp_
             for (int p = 0; p < 64; ++p) s = fmaf(D[o * GEN_PS + p], pes[k * GEN_PS + p], s);
             gen_acc(gp + ndp_off_W0(&d) + idx, first, s);
         }
+        if (DX && t < 192 && base + (t & 63) < (size_t)job.n) {
+            const int p = t & 63, k = t >> 6;                        // (k is wave-uniform: the W0 reads are)
+            const float *w = job.params + ndp_off_W0(&d) + 2 * k;
+            float dsin = 0.f, dcos = 0.f;
+            for (int o = 0; o < W; ++o) {
+                const float z = D[o * GEN_PS + p];
+                dsin = fmaf(z, w[6 * o], dsin);
+                dcos = fmaf(z, w[6 * o + 1], dcos);
+            }
+            float *q = dx + (base + p) * 3 + k;
+            *q += freq * (pes[(2 * k + 1) * GEN_PS + p] * dsin - pes[2 * k * GEN_PS + p] * dcos);
+        }
         __syncthreads();                                             // the next tile's loads overwrite I / dOs / pes
     }
 }
@@ -327,6 +344,14 @@ k_gen_level_bwd(HeadCfg hc, ndp_layer_desc d, BwdJob job, int p_stride) {
     job.tile0 = blockIdx.x;
     job.tile_step = gridDim.x;
     gen_level_bwd_body(hc, d, job, sm);
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_gen_level_bwd_dx(HeadCfg hc, ndp_layer_desc d, BwdJob job, int p_stride, float *dx, float freq) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    job.gpart = job.gpart + (size_t)blockIdx.x * p_stride;
+    job.tile0 = blockIdx.x;
+    job.tile_step = gridDim.x;
+    gen_level_bwd_body<true>(hc, d, job, sm, dx, freq);
 }
 
 // engine stage 3 (both backward stages of the 128 / 3 kernels in one): blockIdx.y = pair, blockIdx.x = partial

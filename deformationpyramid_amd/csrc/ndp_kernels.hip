@@ -502,6 +502,11 @@ enum : int {
     LB_TOTAL = LB_WH + NDP_WHROWS * NDP_W
 };
 static_assert(6 * NDP_PES <= NDP_WHROWS * NDP_W, "posenc rows must fit the shared slot");
+// bwd1 with the input gradient (DX): W0 [128][6] in the dO slot (bwd1 stages no dO), and behind the posenc rows the partial
+// sums of dpe = dz0 . W0 over either half of the outputs, [half][channel][point]
+#define LB1_DPE (LB_PE + 448)
+static_assert(NDP_W * 6 <= 64 * 17, "W0 must fit the dO slot");
+static_assert(6 * NDP_PES <= 448 && 448 + 2 * 6 * 64 <= NDP_WHROWS * NDP_W, "dpe partials must fit behind the posenc rows");
 static constexpr int kSmemBwdBytes = LB_TOTAL * 4;       // 77.1 KB: two workgroups per CU
 static_assert(2 * kSmemBwdBytes <= 160 * 1024, "backward LDS carve must allow two workgroups per CU");
 
@@ -764,7 +769,14 @@ __device__ __forceinline__ void bwd2_body(const HeadCfg &hc, const BwdJob &job, 
 
 // hidden layer 1 and the input layer: dW1 += dz1^T h0 ; db1 ; dh0 = dz1 W1 ; dz0 = dh0 * [h0 > 0] ;
 // [dW0 | db0]^T += [pe | 1]^T dz0 (16x16x4 MFMA: rows = the 6 posenc channels and a row of ones, columns = this wave's 32 outputs)
-__device__ __forceinline__ void bwd1_body(const HeadCfg &hc, const BwdJob &job, float *sm) {
+// DX (the stand-alone operator when dL/dx is asked for; the engine's samples are detached): after the dW0 stage
+//   dpe[p][c] = sum_o dz0[p][o] W0[o][c] ;  dx[p][k] += freq (pe[2k+1][p] dpe[p][2k] - pe[2k][p] dpe[p][2k+1])
+// (pe = [sin, cos] per axis; dx holds the direct term of k_head_bwd_dx).  The contraction is 64 x 6 x 128 per tile next to
+// 2 x 64 x 128 x 128 on the matrix pipe, so it runs as fmaf chains on the VALU, which idles under the MFMA stages: for point
+// p = lane, wave w sums half w & 1 of the outputs (o ascending) for the channels 3 (w >> 1) .. + 2; the halves are then added, lower
+// first.  A tile belongs to one workgroup and a point to one thread: plain read-modify-write in a fixed order, independent of the grid.
+template <bool DX = false>
+__device__ __forceinline__ void bwd1_body(const HeadCfg &hc, const BwdJob &job, float *sm, float *dx = nullptr, float freq = 0.f) {
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int l15 = lane & 15, lk = lane >> 4;
     float *bufA = sm + LB_BUFA, *bufB = sm + LB_BUFB, *pe = sm + LB_PE;
@@ -781,6 +793,10 @@ __device__ __forceinline__ void bwd1_body(const HeadCfg &hc, const BwdJob &job, 
 #pragma unroll
     for (int r = 0; r < 4; ++r) { gW0a[r] = 0.f; gW0b[r] = 0.f; }
     float gb1[4] = {0.f, 0.f, 0.f, 0.f};
+    if (DX) {                                      // (published by the first barrier of the tile loop)
+        const float *W0 = job.params + ndp_off_W0(&dd);
+        for (int i = t; i < NDP_W * 6; i += 256) sm[LB_DO + i] = W0[i];
+    }
 
     // the h0 tile (bufA) of tile i+1 is requested as soon as tile i is done with it, under tile i's dW0 stage
     if (job.tile0 < job.n_tiles) glds_tile(job.act + (size_t)job.tile0 * NDP_TILE * NDP_W, bufA);
@@ -831,6 +847,35 @@ __device__ __forceinline__ void bwd1_body(const HeadCfg &hc, const BwdJob &job, 
                 const float b0 = br[0], b1 = br[16];
                 gW0a = MFMA16(a, b0, gW0a);
                 gW0b = MFMA16(a, b1, gW0b);
+            }
+        }
+        if (DX) {
+            float *dpe = sm + LB1_DPE;
+            {
+                const int oh = wv & 1, c0 = 3 * (wv >> 1);
+                const float *zr = bufB + bp_row(lane) + 64 * oh;                  // dz0[p = lane][64 oh ..]
+                const float *wq = sm + LB_DO + 6 * 64 * oh + c0;                  // W0[64 oh ..][c0 ..]: wave-uniform (broadcast) reads
+                float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float4 z4 = *reinterpret_cast<const float4 *>(zr + 4 * i);
+                    const float z[4] = {z4.x, z4.y, z4.z, z4.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float *w = wq + 6 * (4 * i + j);
+                        s0 = fmaf(z[j], w[0], s0); s1 = fmaf(z[j], w[1], s1); s2 = fmaf(z[j], w[2], s2);
+                    }
+                }
+                float *dq = dpe + (6 * oh + c0) * 64 + lane;
+                dq[0] = s0; dq[64] = s1; dq[128] = s2;
+            }
+            __syncthreads();
+            if (wv < 3 && base + lane < job.n) {                                  // wave k: axis k of the tile's points
+                const float *ds = dpe + (2 * wv) * 64 + lane, *dc = ds + 64;
+                const float dsin = ds[0] + ds[6 * 64], dcos = dc[0] + dc[6 * 64];
+                const float sn = pe[2 * wv * NDP_PES + lane], cs = pe[(2 * wv + 1) * NDP_PES + lane];
+                float *q = dx + (size_t)(base + lane) * 3 + wv;
+                *q += freq * (cs * dsin - sn * dcos);
             }
         }
         PT(6);
@@ -885,21 +930,48 @@ k_level_bwd1(HeadCfg hc, BwdJob job, int p_stride) {
     bwd1_body(hc, job, sm);
 }
 
+// k_level_bwd1 that also adds the part of dL/dx that passes through the network to dx [n][3] (ndp_level_bwd with dx)
+extern "C" __global__ void __launch_bounds__(256, 2)
+k_level_bwd1_dx(HeadCfg hc, BwdJob job, int p_stride, float *dx, float freq) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    job.tile0 = blockIdx.x;
+    job.tile_step = gridDim.x;
+    job.gpart += (size_t)blockIdx.x * p_stride;
+    bwd1_body<true>(hc, job, sm, dx, freq);
+}
+
 // dO[p][16] = mlp_scale * dL/d(scaled head outputs) for p < n, zero rows up to `plane`
-extern "C" __global__ void __launch_bounds__(256)
-k_head_bwd(HeadCfg hc, const float *x, const float *heads, const float *g, const float *g_nr, int n, int plane, float *dO) {
-    __shared__ __attribute__((aligned(16))) float rows[256 * NDP_NHMAX];
+// DX: dx[p][3] = the direct part of dL/dx (head_warp_bwd) as well
+template <bool DX>
+__device__ __forceinline__ void head_bwd_body(const HeadCfg &hc, const float *x, const float *heads, const float *g, const float *g_nr,
+                                              int n, int plane, float *dO, float *dx, float *rows) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= plane) return;
     float *out = dO + (size_t)p * NDP_NHMAX;
     if (p < n) {
         const float xv[3] = {x[3 * p], x[3 * p + 1], x[3 * p + 2]};
         const float gv[3] = {g[3 * p], g[3 * p + 1], g[3 * p + 2]};
-        point_head_bwd(hc, heads + (size_t)p * NDP_HROW, xv, gv, g_nr ? g_nr[p] : 0.f, rows + threadIdx.x * NDP_NHMAX, out);
+        if (DX) {
+            float dv[3];
+            point_head_bwd(hc, heads + (size_t)p * NDP_HROW, xv, gv, g_nr ? g_nr[p] : 0.f, rows + threadIdx.x * NDP_NHMAX, out, nullptr, dv);
+            dx[3 * p] = dv[0]; dx[3 * p + 1] = dv[1]; dx[3 * p + 2] = dv[2];
+        } else {
+            point_head_bwd(hc, heads + (size_t)p * NDP_HROW, xv, gv, g_nr ? g_nr[p] : 0.f, rows + threadIdx.x * NDP_NHMAX, out);
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < NDP_NHMAX; j += 4) *reinterpret_cast<float4 *>(out + j) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_head_bwd(HeadCfg hc, const float *x, const float *heads, const float *g, const float *g_nr, int n, int plane, float *dO) {
+    __shared__ __attribute__((aligned(16))) float rows[256 * NDP_NHMAX];
+    head_bwd_body<false>(hc, x, heads, g, g_nr, n, plane, dO, nullptr, rows);
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_head_bwd_dx(HeadCfg hc, const float *x, const float *heads, const float *g, const float *g_nr, int n, int plane, float *dO, float *dx) {
+    __shared__ __attribute__((aligned(16))) float rows[256 * NDP_NHMAX];
+    head_bwd_body<true>(hc, x, heads, g, g_nr, n, plane, dO, dx, rows);
 }
 
 extern "C" __global__ void k_grad_reduce(const float *gpart, int n_part, int p_stride, int P, float *grads) {
@@ -2382,7 +2454,7 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 #ifndef NDP_BUILD_ID
 #define NDP_BUILD_ID "unversioned"
 #endif
-extern "C" int ndp_version(void) { return 204; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written; 204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]
+extern "C" int ndp_version(void) { return 205; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written; 204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]; 205: ndp_level_bwd gained the trailing `dx` (dL/dx of the level's input points, may be NULL)
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }
@@ -2425,14 +2497,18 @@ extern "C" int ndp_level_fwd(const ndp_layer_desc *desc, const float *params, in
 
 extern "C" int ndp_level_bwd(const ndp_layer_desc *desc, const float *params, int level, int k0,
                              const float *x, int n, float *act, const float *heads, const float *g, const float *g_nr,
-                             float *dO_work, float *grads_part, int n_part, int p_stride, void *stream) {
-    (void)level; (void)k0;
+                             float *dO_work, float *grads_part, int n_part, int p_stride, void *stream, float *dx) {
     if (int rc = check_desc(desc)) return rc;
     if (n <= 0 || !params || !x || !act || !heads || !g || !dO_work || !grads_part || n_part < 1)
         return fail(NDP_E_INVALID, "ndp_level_bwd: null pointer / bad sizes");
     if (p_stride < ndp_param_count(desc)) return fail(NDP_E_INVALID, "ndp_level_bwd: p_stride < P");
     if (!aligned16(params) || !aligned16(act) || !aligned16(heads) || !aligned16(dO_work))
         return fail(NDP_E_INVALID, "ndp_level_bwd: params/act/heads/dO_work must be 16-byte aligned");
+    // dx needs the level's frequency 2^(level + 1 + k0): a finite, normal float
+    if (dx && (level < 0 || level >= NDP_MAX_LEVELS || level + 1 + k0 < -126 || level + 1 + k0 > 127))
+        return fail(NDP_E_INVALID, "ndp_level_bwd: dx needs 0 <= level < 16 and 2^(level + 1 + k0) in float range");
+    if (dx && ((uintptr_t)dx & 3)) return fail(NDP_E_INVALID, "ndp_level_bwd: dx must be 4-byte aligned");
+    const float freq = dx ? ldexpf(1.0f, level + 1 + k0) : 0.f;
     BwdJob job;
     memset(&job, 0, sizeof job);
     job.params = params; job.act = act; job.heads = heads; job.dO = dO_work; job.gpart = grads_part;
@@ -2445,11 +2521,17 @@ extern "C" int ndp_level_bwd(const ndp_layer_desc *desc, const float *params, in
         n_part = job.n_tiles;
     }
     const HeadCfg hc = make_head_cfg(*desc);
-    hipLaunchKernelGGL(k_head_bwd, dim3((job.plane + 255) / 256), dim3(256), 0, s, hc, x, heads, g,
-                       desc->nonrigidity ? g_nr : nullptr, n, job.plane, dO_work);
+    // dx: the head backward leaves the direct part of dL/dx there, the level backward adds the part through the network
+    if (dx) hipLaunchKernelGGL(k_head_bwd_dx, dim3((job.plane + 255) / 256), dim3(256), 0, s, hc, x, heads, g,
+                               desc->nonrigidity ? g_nr : nullptr, n, job.plane, dO_work, dx);
+    else hipLaunchKernelGGL(k_head_bwd, dim3((job.plane + 255) / 256), dim3(256), 0, s, hc, x, heads, g,
+                            desc->nonrigidity ? g_nr : nullptr, n, job.plane, dO_work);
     if (gen_is_generic(*desc)) {
         if (int rc = set_smem((const void *)k_gen_level_bwd, kSmemGenBwdMax)) return rc;
-        hipLaunchKernelGGL(k_gen_level_bwd, dim3(n_part), dim3(256), gen_bwd_floats(desc->width) * 4, s, hc, *desc, job, p_stride);
+        if (dx) {
+            if (int rc = set_smem((const void *)k_gen_level_bwd_dx, kSmemGenBwdMax)) return rc;
+            hipLaunchKernelGGL(k_gen_level_bwd_dx, dim3(n_part), dim3(256), gen_bwd_floats(desc->width) * 4, s, hc, *desc, job, p_stride, dx, freq);
+        } else hipLaunchKernelGGL(k_gen_level_bwd, dim3(n_part), dim3(256), gen_bwd_floats(desc->width) * 4, s, hc, *desc, job, p_stride);
         HIP_TRY(hipGetLastError(), "generic level backward launch");
         return 0;
     }
@@ -2459,7 +2541,10 @@ extern "C" int ndp_level_bwd(const ndp_layer_desc *desc, const float *params, in
     job.h_plane = act + (size_t)job.plane * NDP_W;
     bwd_job_ndp_layer2(job, hc.nh);
     hipLaunchKernelGGL(k_level_bwd2, dim3(n_part), dim3(256), kSmemBwdBytes, s, hc, job, p_stride);
-    hipLaunchKernelGGL(k_level_bwd1, dim3(n_part), dim3(256), kSmemBwdBytes, s, hc, job, p_stride);
+    if (dx) {
+        if (int rc = set_smem((const void *)k_level_bwd1_dx, kSmemBwdBytes)) return rc;
+        hipLaunchKernelGGL(k_level_bwd1_dx, dim3(n_part), dim3(256), kSmemBwdBytes, s, hc, job, p_stride, dx, freq);
+    } else hipLaunchKernelGGL(k_level_bwd1, dim3(n_part), dim3(256), kSmemBwdBytes, s, hc, job, p_stride);
     HIP_TRY(hipGetLastError(), "level backward launch");
     return 0;
 }

@@ -29,8 +29,9 @@ def _lengths(points, lengths, name):
 
 def compute_truncated_chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None,
                                        weights=None, trunc=0.2, batch_reduction="mean", point_reduction="mean"):
-    """Bidirectional L1 Chamfer on exact 1-NN with truncation in SQUARED units.  Differentiable
-    with respect to x (the only use on the hot path: registration.py:195,212)."""
+    """Bidirectional L1 Chamfer on exact 1-NN with truncation in SQUARED units.  Differentiable (first derivatives) in x -- the
+    only use on the hot path: registration.py:195,212 -- and in y: whichever of the two requires a gradient receives one, from the
+    one nearest-neighbour search."""
     if batch_reduction is not None and batch_reduction not in ["mean", "sum"]:
         raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
     if point_reduction not in ["mean", "sum"]:

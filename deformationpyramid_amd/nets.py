@@ -13,8 +13,11 @@ What is different underneath: every level's parameters live in ONE flat float32 
 (layout.py / include/ndp_types.h) and all m blocks are rows of a single [m, Pmax] tensor in
 HBM; the per-name nn.Parameters are views into it.  `warp` runs the hand-written HIP level
 kernels (csrc/) through torch.autograd.Function wrappers, so callers that own their Adam loop
-(shape_transfer.py:116-157 style) keep working.  There is no PyTorch fallback: on a CUDA/HIP
-device the native library must be loaded; on CPU tensors `warp` raises.
+(shape_transfer.py:116-157 style) keep working.  Like the reference's autograd code, `warp` is
+differentiable (first derivatives) in the parameters of every level that requires a gradient AND in
+its input points: several levels can be trained at once, and points can be optimised through a
+frozen pyramid.  There is no PyTorch fallback: on a CUDA/HIP device the native library must be
+loaded; on CPU tensors `warp` raises.
 
 Initialisation replays the reference's RNG consumption exactly (nets.py:75-109,180-183):
 default nn.Linear init for weights and biases in module-registration order, then
@@ -203,6 +206,28 @@ class Deformation_Pyramid:
         store = init_pyramid_store(self.descs, depth, self.p_stride)
         self.store = store.to(self.device)
         self.pyramid = [NDPLevel(d, i, k0, self.store[i, :d.param_count]) for i, d in enumerate(self.descs)]
+
+    @classmethod
+    def from_store(cls, store, depth, width, k0, rotation_format, nonrigidity_est=False, motion='SE3'):
+        """A pyramid over an existing [m, p_stride] parameter block (level l in row l, layout.py) -- e.g. a fitted one
+        (Registration.fitted_pyramid).  The block is used as it is, not copied; no random number is drawn."""
+        assert motion in ["Sim3", "SE3", "sflow"]
+        if store.dim() != 2 or store.dtype != torch.float32 or not store.is_contiguous():
+            raise ValueError("store must be a contiguous float32 [m, p_stride] block")
+        self = cls.__new__(cls)
+        m = store.shape[0]
+        self.depth, self.width, self.k0 = depth, width, k0
+        self.n_hierarchy = m
+        self.device = store.device
+        self.descs = [LayerDesc(width=width, n_hidden=depth - 1, motion=motion, rotfmt=rotation_format,
+                                nonrigidity=bool(nonrigidity_est) and (i != 0)) for i in range(m)]
+        self.pmax = max(d.param_count for d in self.descs) if m else 0
+        self.p_stride = store.shape[1]
+        if self.p_stride < self.pmax or self.p_stride % 4:
+            raise ValueError(f"store rows must hold {self.pmax} parameters and stay 16-byte aligned, got p_stride = {self.p_stride}")
+        self.store = store
+        self.pyramid = [NDPLevel(d, i, k0, self.store[i, :d.param_count]) for i, d in enumerate(self.descs)]
+        return self
 
     def warp(self, x, max_level=None, min_level=0):
         if max_level is None:

@@ -8,6 +8,7 @@ import ctypes
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from .layout import LayerDesc
@@ -57,8 +58,10 @@ def level_fwd(desc: LayerDesc, params, level, k0, x, save=False, want_nonrig=Fal
     return res if len(res) > 1 else res[0]
 
 
-def level_bwd(desc: LayerDesc, params, level, k0, x, act, heads, g, n_part=None, g_nr=None):
-    """-> grads [P] (partials folded in index order on the device).  `act` is consumed."""
+def level_bwd(desc: LayerDesc, params, level, k0, x, act, heads, g, n_part=None, g_nr=None, want_dx=False):
+    """-> grads [P] (partials folded in index order on the device).  `act` is consumed.
+    want_dx: -> (grads, dx [n,3]) with dx = dL/dx of the level's input points (the warp's own dependence on x plus the path
+    through the positional encoding and the network); grads are the same bits with and without."""
     _chk(params, "params"); _chk(x, "x"); _chk(act, "act"); _chk(heads, "heads"); _chk(g, "g")
     if g_nr is not None:
         _chk(g_nr, "g_nr")
@@ -74,11 +77,12 @@ def level_bwd(desc: LayerDesc, params, level, k0, x, act, heads, g, n_part=None,
     work = torch.empty(cap(n), N.NHMAX, device=x.device, dtype=torch.float32)
     cd = desc.c_struct()
     st = N.stream_ptr(x.device)
+    dx = torch.empty_like(x) if want_dx else None
     N.check(N.lib().ndp_level_bwd(ctypes.byref(cd), _p(params), int(level), int(k0), _p(x), n, _p(act), _p(heads),
-                                  _p(g), _p(g_nr), _p(work), _p(part), n_part, stride, st), "ndp_level_bwd")
+                                  _p(g), _p(g_nr), _p(work), _p(part), n_part, stride, st, _p(dx)), "ndp_level_bwd")
     grads = torch.empty(P, device=x.device, dtype=torch.float32)
     N.check(N.lib().ndp_grad_reduce(_p(part), n_part, stride, P, _p(grads), st), "ndp_grad_reduce")
-    return grads
+    return (grads, dx) if want_dx else grads
 
 
 def pyramid_fwd(desc: LayerDesc, m, k0, store, x):
@@ -164,8 +168,10 @@ def chamfer_nn_onepass(x, y, matrix=False):
     return d2x, ix, d2y, iy
 
 
-def chamfer_l1(x, y, trunc, nn=None, want_grad=True, point_sum=False):
-    """-> (loss [1], gx [S,3] | None, nn tuple).  point_sum: point_reduction="sum" of loss.py:233-235."""
+def chamfer_l1(x, y, trunc, nn=None, want_grad=True, point_sum=False, want_grad_y=False):
+    """-> (loss [1], gx [S,3] | None, nn tuple).  point_sum: point_reduction="sum" of loss.py:233-235.
+    want_grad_y: -> (loss, gx, nn, gy [T,3]).  The loss is symmetric in its clouds, so gy is the same kernel with the two clouds and
+    their halves of the ONE nearest-neighbour result exchanged: the bits of chamfer_l1(y, x)'s gx."""
     if nn is None:
         nn = chamfer_nn(x, y)
     d2x, ix, d2y, iy = nn
@@ -173,7 +179,13 @@ def chamfer_l1(x, y, trunc, nn=None, want_grad=True, point_sum=False):
     gx = torch.empty_like(x) if want_grad else None
     N.check(N.lib().ndp_chamfer_l1_bwd(_p(x), x.shape[0], _p(y), y.shape[0], float(trunc), _p(d2x), _p(ix), _p(d2y),
                                        _p(iy), _p(loss), _p(gx), 1 if point_sum else 0, N.stream_ptr(x.device)), "ndp_chamfer_l1_bwd")
-    return loss, gx, nn
+    if not want_grad_y:
+        return loss, gx, nn
+    gy = torch.empty_like(y)
+    loss_y = torch.empty(1, device=x.device)                         # (the exchanged call's own copy of the value: not used)
+    N.check(N.lib().ndp_chamfer_l1_bwd(_p(y), y.shape[0], _p(x), x.shape[0], float(trunc), _p(d2y), _p(iy), _p(d2x),
+                                       _p(ix), _p(loss_y), _p(gy), 1 if point_sum else 0, N.stream_ptr(x.device)), "ndp_chamfer_l1_bwd")
+    return loss, gx, nn, gy
 
 
 def landmark_mse(x, t):
@@ -203,12 +215,15 @@ def adam_step(p, g, m, v, t, lr=0.01, b1=0.9, b2=0.999, eps=1e-8):
 # ------------------------------------------------------------------------------ autograd wrappers
 class _LevelWarpFn(torch.autograd.Function):
     """NDPLayer.forward (nets.py:111-140) for callers that own their optimisation loop
-    (shape_transfer.py:116-157).  x is treated as detached, as on the reference's hot path.
+    (shape_transfer.py:116-157).  Differentiable in the level's parameters AND in x, like the reference's autograd code: levels
+    chained by Deformation_Pyramid.warp pass the gradient down, and points can be optimised through a frozen pyramid.  When x does
+    not require a gradient the launches are those of a detached x (the reference's hot path).  First derivatives only.
     Returns (x', nonrigidity) -- the gate tensor is empty for levels without the nonrigidity head."""
 
     @staticmethod
     def forward(ctx, x, layer, *params):
-        need = any(p.requires_grad for p in params)
+        need_p = any(p.requires_grad for p in params)
+        need = need_p or x.requires_grad
         flat = layer.flat.detach()
         xd = x.detach().contiguous()
         gate = layer.desc.nonrigidity
@@ -217,6 +232,7 @@ class _LevelWarpFn(torch.autograd.Function):
             out, act, heads, nr = res
             ctx.save_for_backward(xd, act, heads)
             ctx.layer = layer
+            ctx.need_p = need_p
         else:
             out, nr = level_fwd(layer.desc, flat, layer.level, layer.k0, xd, want_nonrig=True)
         if not gate:
@@ -225,18 +241,24 @@ class _LevelWarpFn(torch.autograd.Function):
         return out, nr
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g, g_nr):
         x, act, heads = ctx.saved_tensors
         layer = ctx.layer
         gnr = g_nr.contiguous() if (layer.desc.nonrigidity and g_nr is not None) else None
-        grads = level_bwd(layer.desc, layer.flat.detach(), layer.level, layer.k0, x, act, heads, g.contiguous(), g_nr=gnr)
+        want_dx = ctx.needs_input_grad[0]
+        res = level_bwd(layer.desc, layer.flat.detach(), layer.level, layer.k0, x, act, heads, g.contiguous(), g_nr=gnr, want_dx=want_dx)
+        grads, dx = res if want_dx else (res, None)
         outs = []
         for name, off, shape in layer.desc.named_slices():
+            if not ctx.need_p:
+                outs.append(None)
+                continue
             n = 1
             for s in shape:
                 n *= s
             outs.append(grads[off:off + n].view(shape))
-        return (None, None) + tuple(outs)
+        return (dx, None) + tuple(outs)
 
 
 def level_warp(layer, x):
@@ -252,18 +274,22 @@ class _ChamferFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, trunc, point_sum=False):
         xd, yd = x.detach().contiguous(), y.detach().contiguous()
-        loss, gx, _ = chamfer_l1(xd, yd, trunc, want_grad=x.requires_grad, point_sum=point_sum)
-        ctx.save_for_backward(gx if gx is not None else torch.empty(0, device=x.device))
+        res = chamfer_l1(xd, yd, trunc, want_grad=x.requires_grad, point_sum=point_sum, want_grad_y=y.requires_grad)
+        loss, gx = res[0], res[1]
+        gy = res[3] if y.requires_grad else None
+        none = torch.empty(0, device=x.device)
+        ctx.save_for_backward(gx if gx is not None else none, gy if gy is not None else none)
         return loss[0]
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
-        (gx,) = ctx.saved_tensors
-        return (gx * g if gx.numel() else None), None, None, None
+        gx, gy = ctx.saved_tensors
+        return (gx * g if gx.numel() else None), (gy * g if gy.numel() else None), None, None
 
 
 def chamfer_distance(x, y, trunc, point_sum=False):
-    """Differentiable (wrt x) truncated L1 Chamfer of two [n,3] clouds."""
+    """Differentiable (in x and in y, first derivatives) truncated L1 Chamfer of two [n,3] clouds."""
     return _ChamferFn.apply(x, y, float(trunc), bool(point_sum))
 
 

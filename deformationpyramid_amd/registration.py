@@ -5,7 +5,12 @@
     warped, iter_cnt, timer = model.register(visualize=False, timer=None)   (:106-123, :126-262)
     model.src_pcd                                      un-centred source on the device (eval_nolearned.py:94)
 
-plus one extension the reference has no counterpart for, because its loop is one pair at a time:
+plus two extensions the reference has no counterpart for.  The fitted weights stay inside the engine; a caller that goes on
+from them (joint refinement of all levels, inverting the warp) gets them as an object:
+
+    pyramid, src_mean, tgt_mean = model.fitted_pyramid()     after register(); pyramid.warp(src - src_mean)[0] + tgt_mean
+
+and, because the reference's loop is one pair at a time:
 
     results = model.register_batch([(src, tgt[, landmarks]), ...], slots=64)
 
@@ -46,6 +51,7 @@ class Registration:
         self.deformation_model = config.deformation_model
         self._engines = {}
         self.last_state = None
+        self._last_fit = None
 
     # ------------------------------------------------------------------ reference surface
     def load_pcds(self, src, tgt, landmarks=None):
@@ -90,10 +96,26 @@ class Registration:
         st = eng.run_until_done(chunk=32, kernel_ms=kernel_ms)[0]
         warped = self._finish(eng, [(0, prep)])[0]
         self.last_state = st
+        self._last_fit = (eng, prep)
         iter_cnt = {lvl: int(st.evals_per_level[lvl]) for lvl in range(self.config.m)}
         if timer is not None:
             self._fill_timer(timer, kernel_ms, st, prep.K > 0)
         return warped, iter_cnt, timer
+
+    def fitted_pyramid(self):
+        """-> (pyramid, src_mean [3], tgt_mean [3]) of the last register(): the fitted weights as a Deformation_Pyramid over a COPY
+        of the engine slot's [m, p_stride] block (writing into it changes nothing a later register() computes), and the two cloud
+        means of registration.py:150-153, such that  pyramid.warp(src - src_mean)[0] + tgt_mean  is the cloud register() returned
+        (bit for bit in the fp32 arithmetic, gemm_mode 0; register()'s own final warp otherwise runs on the fp16-split contractions).
+        Its levels are nn.Modules with trainable parameters, and warp() is differentiable in them and in its points."""
+        if self._last_fit is None:
+            raise RuntimeError("fitted_pyramid(): no fitted pyramid yet -- call register() (deformation_model NDP) first")
+        from .nets import Deformation_Pyramid
+        eng, prep = self._last_fit
+        c = self.config
+        pyramid = Deformation_Pyramid.from_store(eng.params[0].clone(), c.depth, c.width, c.k0, c.rotation_format,
+                                                 nonrigidity_est=c.w_reg > 0, motion=c.motion_type)
+        return pyramid, prep.means[0:3].clone(), prep.means[4:7].clone()
 
     @staticmethod
     def _fill_timer(timer, kernel_ms, st, has_ldmk):
@@ -129,6 +151,7 @@ class Registration:
         pairs = list(pairs)
         if not pairs:
             return []
+        self._last_fit = None                                    # the engine slots are about to be refilled
         # one engine configuration serves the whole batch: capacities from the LARGEST landmark set (landmarks are known
         # before any preparation), and the objective (w_cd / trunc_cd, registration.py:189-212) must be the same for all
         ks = [int(item[2][0].shape[0]) if len(item) > 2 and item[2] is not None else 0 for item in pairs]

@@ -54,14 +54,18 @@ int ndp_level_fwd(const ndp_layer_desc *desc, const float *params, int level, in
                   const float *x, int n, float *x_out, float *act, float *heads, float *nonrig_out,
                   void *stream);
 
-/* Backward of one level wrt its parameters given g = dL/dx_out [n][3] (autograd of nets.py:111-140;
- * x is a detached input, registration.py:243-249).  act/heads come from ndp_level_fwd on the same
+/* Backward of one level given g = dL/dx_out [n][3] (autograd of nets.py:111-140): wrt its parameters, and -- when dx is
+ * given -- wrt its input points.  act/heads come from ndp_level_fwd on the same
  * x and params; act is CONSUMED at 128 / 3 (its h2 plane is overwritten with an intermediate; the generic kernels leave it).  dO_work is
  * scratch of [n_cap][16] floats; g_nr (may be NULL) = dL/d(gate) [n] when desc->nonrigidity.  grads_part [n_part][P_stride] receives n_part partial sums
- * (deterministic: workgroup g sums tiles g, g+n_part, ...); ndp_grad_reduce folds them in index order. */
+ * (deterministic: workgroup g sums tiles g, g+n_part, ...); ndp_grad_reduce folds them in index order.
+ *   dx (may be NULL): [n][3] receives dL/dx, the warp's own dependence on x plus the path through the positional encoding and the
+ *       network (f = 2^(level + 1 + k0); every point is written by one thread in a fixed order: reproducible, independent of n_part).
+ *       NULL: x is a detached input (the reference's hot path, registration.py:243-249) -- the launches and the results of ABI 204;
+ *       level / k0 are read only when dx is given.  The parameter gradients are the same bits either way.                        */
 int ndp_level_bwd(const ndp_layer_desc *desc, const float *params, int level, int k0,
                   const float *x, int n, float *act, const float *heads, const float *g, const float *g_nr,
-                  float *dO_work, float *grads_part, int n_part, int p_stride, void *stream);
+                  float *dO_work, float *grads_part, int n_part, int p_stride, void *stream, float *dx);
 
 /* grads[P] = sum_{g<n_part} grads_part[g][:]  (fixed order). */
 int ndp_grad_reduce(const float *grads_part, int n_part, int p_stride, int P, float *grads, void *stream);

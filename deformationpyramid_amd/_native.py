@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libndp_hip.so")
 SOURCES = ["ndp_kernels.hip"]
-HEADERS = ["ndp_device.h", "ndp_nerfies.inc", "ndp_ed.inc", "ndp_fwd_split.inc", "ndp_bwd_split.inc", "ndp_bwd_fused.inc", "ndp_nn_matrix.inc", "ndp_generic.inc", os.path.join("..", "..", "include", "ndp_hip.h"), os.path.join("..", "..", "include", "ndp_types.h")]
+HEADERS = ["ndp_device.h", "ndp_nerfies.inc", "ndp_ed.inc", "ndp_fwd_split.inc", "ndp_bwd_split.inc", "ndp_bwd_fused.inc", "ndp_nn_matrix.inc", "ndp_generic.inc", "ndp_jacobian.inc", os.path.join("..", "..", "include", "ndp_hip.h"), os.path.join("..", "..", "include", "ndp_types.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-pass-failed"]
 
 NDP_MAX_LEVELS = 16
@@ -150,6 +150,8 @@ _SIGS = {
     "ndp_level_bwd": [DP, V, I, I, V, I, V, V, V, V, V, V, I, I, V, V],
     "ndp_grad_reduce": [V, I, I, I, V, V],
     "ndp_pyramid_fwd": [DP, I, I, V, I, V, I, V, V],
+    "ndp_pyramid_jac": [DP, I, I, V, I, I, I, V, I, V, V, V, V, V],
+    "ndp_pyramid_inverse": [DP, I, I, V, I, I, I, V, I, V, I, F, V, V, V],
     "ndp_pyramid_fwd_batch": [DP, I, I, I, ctypes.POINTER(WarpJob), I, V],
     "ndp_pyramid_fwd_batch_split": [DP, I, I, I, ctypes.POINTER(WarpJob), I, V],
     "ndp_pyramid_fwd_batch_split_tiles": [DP, I, I, I, ctypes.POINTER(WarpJob), I, I, V],

@@ -23,6 +23,7 @@ Initialisation replays the reference's RNG consumption exactly (nets.py:75-109,1
 default nn.Linear init for weights and biases in module-registration order, then
 xavier_uniform_ on every matrix, for all m levels up front, on the CPU generator.
 """
+import collections
 import math
 
 import torch
@@ -30,6 +31,8 @@ import torch.nn as nn
 
 from .layout import LayerDesc
 
+
+InverseInfo = collections.namedtuple("InverseInfo", "converged residual iterations")
 
 _KAIMING_GAIN = nn.init.calculate_gain("leaky_relu", math.sqrt(5))
 
@@ -238,6 +241,45 @@ class Deformation_Pyramid:
             x, nonrigidity = self.pyramid[i](x)
             data[i] = (x, nonrigidity)
         return x, data
+
+    def _level_args(self, x, max_level, min_level):
+        if max_level is None:
+            max_level = self.n_hierarchy - 1
+        assert 0 <= min_level <= max_level < self.n_hierarchy, "more level than defined"
+        if x.dim() != 2 or x.shape[-1] != 3:
+            raise ValueError("expected points of shape [n, 3]")
+        # descs[-1] carries the library's convention "every level but the first is gated" (nets.py:26)
+        return self.descs[-1], self.store.detach(), x.detach().float().contiguous(), min_level, max_level
+
+    def warp_jacobian(self, x, max_level=None, min_level=0):
+        """-> (x', J [n,3,3]) with J[p, a, b] = d x'_a / d x_b of warp(x, max_level, min_level), from ONE launch of the fused
+        warp-and-Jacobian kernel.  x' is bit for bit warp()'s.  Detached tensors, first-order values only: nothing here joins the
+        autograd graph (for gradients use warp())."""
+        from . import ops
+        d, store, xd, lo, hi = self._level_args(x, max_level, min_level)
+        return ops.pyramid_jacobian(d, self.n_hierarchy, self.k0, store, xd, lo, hi)
+
+    def warp_normals(self, x, normals, max_level=None, min_level=0):
+        """-> (x', n') with n' = cof(J) n / |cof(J) n|: the normals of an oriented cloud or a mesh carried along by the warp (J^-T n
+        up to the factor det J; where the field folds, det J < 0, the sign follows the cofactor matrix).  Detached tensors,
+        first-order values only: nothing here joins the autograd graph."""
+        from . import ops
+        d, store, xd, lo, hi = self._level_args(x, max_level, min_level)
+        out, _, nout = ops.pyramid_jacobian(d, self.n_hierarchy, self.k0, store, xd, lo, hi, normals=normals.detach().float().contiguous())
+        return out, nout
+
+    def inverse_warp(self, y, max_level=None, min_level=0, x0=None, iters=8, tol=2e-6):
+        """Points of the warped frame back into the input frame: solves warp(x) = y by Newton's method from x0 (None: y), all
+        iterations inside one launch.  -> (x, info) with info = (converged bool [n], residual [n] = max |warp(x) - y| of the x
+        returned, iterations int32 [n]: Newton steps taken, -1 not converged within iters, -2 singular Jacobian or non-finite
+        values).  There is no line search: where the field folds (det J <= 0) points may not converge, and info says which.
+        Detached tensors, first-order values only: nothing here joins the autograd graph."""
+        from . import ops
+        d, store, yd, lo, hi = self._level_args(y, max_level, min_level)
+        if x0 is not None:
+            x0 = x0.detach().float().contiguous()
+        x, res, status = ops.pyramid_inverse(d, self.n_hierarchy, self.k0, store, yd, lo, hi, x0=x0, iters=iters, tol=tol)
+        return x, InverseInfo(status >= 0, res, status)
 
     def gradient_setup(self, optimized_level):
         assert optimized_level < self.n_hierarchy, "more level than defined"

@@ -95,6 +95,52 @@ def pyramid_fwd(desc: LayerDesc, m, k0, store, x):
     return out
 
 
+def _levels(m, min_level, max_level):
+    max_level = int(m) - 1 if max_level is None else int(max_level)
+    return int(min_level), max_level
+
+
+def pyramid_jacobian(desc: LayerDesc, m, k0, store, x, min_level=0, max_level=None, normals=None):
+    """The warp of levels min_level..max_level and its per-point Jacobian in one launch (csrc/ndp_jacobian.inc).
+    store [m, p_stride], x [n,3] -> (x' [n,3], J [n,3,3]) with J[p, a, b] = d x'_a / d x_b; with normals [n,3] also
+    n' = cof(J) n / |cof(J) n| (J^-T n up to the factor det J; its sign follows the cofactor matrix where det J < 0).
+    x' is bit for bit pyramid_fwd's.  desc.nonrigidity means "every level but the first is gated", as for pyramid_fwd."""
+    _chk(store, "store"); _chk(x, "x")
+    if normals is not None:
+        _chk(normals, "normals")
+        if normals.shape != x.shape:
+            raise N.NdpError("pyramid_jacobian: normals must have the shape of x")
+    lo, hi = _levels(m, min_level, max_level)
+    n = x.shape[0]
+    out = torch.empty_like(x)
+    J = torch.empty(n, 3, 3, device=x.device, dtype=torch.float32)
+    nout = torch.empty_like(x) if normals is not None else None
+    cd = desc.c_struct()
+    N.check(N.lib().ndp_pyramid_jac(ctypes.byref(cd), int(m), int(k0), _p(store), store.stride(0), lo, hi, _p(x), n, _p(out), _p(J),
+                                    _p(normals), _p(nout), N.stream_ptr(x.device)), "ndp_pyramid_jac")
+    return (out, J) if normals is None else (out, J, nout)
+
+
+def pyramid_inverse(desc: LayerDesc, m, k0, store, y, min_level=0, max_level=None, x0=None, iters=8, tol=2e-6):
+    """Newton on warp(x) = y for levels min_level..max_level, every iteration inside one launch.  y [n,3]; x0 [n,3] the first guess
+    (None: y) -> (x [n,3], residual [n] = max |warp(x) - y| of the x returned, status [n] int32: Newton steps taken when converged,
+    -1 not converged within iters, -2 stopped on a singular Jacobian or non-finite values)."""
+    _chk(store, "store"); _chk(y, "y")
+    lo, hi = _levels(m, min_level, max_level)
+    n = y.shape[0]
+    if x0 is not None:
+        _chk(x0, "x0")
+        if x0.shape != y.shape:
+            raise N.NdpError("pyramid_inverse: x0 must have the shape of y")
+    x = (y if x0 is None else x0).clone()
+    res = torch.empty(n, device=y.device, dtype=torch.float32)
+    status = torch.empty(n, device=y.device, dtype=torch.int32)
+    cd = desc.c_struct()
+    N.check(N.lib().ndp_pyramid_inverse(ctypes.byref(cd), int(m), int(k0), _p(store), store.stride(0), lo, hi, _p(y), n, _p(x), int(iters),
+                                        float(tol), _p(res), _p(status), N.stream_ptr(y.device)), "ndp_pyramid_inverse")
+    return x, res, status
+
+
 def pyramid_fwd_batch(desc: LayerDesc, m, k0, jobs, device=None, split=False, tiles=None):
     """jobs: [(store [m,p_stride], x [n,3], shift_in [>=3] | None, shift_out [>=3] | None)] -> [x_out [n,3]]: every
     cloud through its whole pyramid in ONE launch per 32 jobs; x_out = pyramid(x - shift_in) + shift_out.

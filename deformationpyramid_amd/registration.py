@@ -117,6 +117,19 @@ class Registration:
                                                  nonrigidity_est=c.w_reg > 0, motion=c.motion_type)
         return pyramid, prep.means[0:3].clone(), prep.means[4:7].clone()
 
+    def inverse_warp(self, points, **kw):
+        """Target-frame points -> the source frame of the last register(): fitted_pyramid().inverse_warp(points - tgt_mean) +
+        src_mean, i.e. the x with  pyramid.warp(x - src_mean) + tgt_mean = points  (label / texture pull-back, target-side scene
+        flow, cycle checks).  **kw: max_level, min_level, x0 (a first guess in the SOURCE frame, the frame of the x returned), iters, tol of
+        Deformation_Pyramid.inverse_warp.  -> (x [n,3], info); info.converged says which points Newton solved.  Before any
+        register() it raises like fitted_pyramid()."""
+        pyramid, src_mean, tgt_mean = self.fitted_pyramid()
+        pts = torch.as_tensor(points, dtype=torch.float32).to(pyramid.store.device)
+        if kw.get("x0") is not None:
+            kw["x0"] = (torch.as_tensor(kw["x0"], dtype=torch.float32).to(pts.device) - src_mean).contiguous()
+        x, info = pyramid.inverse_warp((pts - tgt_mean).contiguous(), **kw)
+        return x + src_mean, info
+
     @staticmethod
     def _fill_timer(timer, kernel_ms, st, has_ldmk):
         """The reference tics `lvl_warp` and `Chamfer` once per loss evaluation (only without landmarks) and `backprop` once per

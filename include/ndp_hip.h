@@ -105,6 +105,37 @@ int ndp_pyramid_fwd_batch_split(const ndp_layer_desc *desc, int m, int k0, int p
 int ndp_pyramid_fwd_batch_split_tiles(const ndp_layer_desc *desc, int m, int k0, int p_stride,
                                       const ndp_warp_job *jobs, int n_jobs, int tiles, void *stream);
 
+/* The warp of levels min_level..max_level together with its per-point Jacobian, in one launch (csrc/ndp_jacobian.inc: a workgroup
+ * carries a 64-point tile and three tangent rows per point through the levels; fp32 MFMA, no fp16 split).
+ *   x [n][3] -> x_out [n][3]: bit for bit what ndp_pyramid_fwd gives for the same levels and input;
+ *   J [n][9] row-major, J[3a+b] = d x_out_a / d x_b (first order; ReLU kinks take the derivative 0 of the level backward);
+ *   normals_in / normals_out (both or neither; may be NULL) [n][3]: n' = cof(J) n / |cof(J) n|, which is J^-T n up to the factor
+ *   det J -- no division by det J, so a fold does not blow up; where det J < 0 the SIGN of n' follows the cofactor matrix, i.e. it is
+ *   opposite to J^-T n (a reflected patch keeps the orientation its cofactor matrix gives it).  A zero cof(J) n gives NaN.
+ *   A cof(J) n whose fp32 squared length is within 2^-21 of 1 counts as unit and is written as it is (unit normals pass an identity
+ *   warp bit for bit); |n'| is 1 to 3e-7 either way.
+ * Refused before any launch (NDP_E_INVALID, NDP_E_UNSUPPORTED for the shape): n <= 0, levels outside 0 <= min_level <= max_level < m
+ * <= 16, p_stride below the parameter count or not a multiple of 4, params_all not 16-byte aligned, NULL or misaligned (4 bytes)
+ * x / x_out / J / normals, one of the normals pointers without the other.  Every point is written by one thread: reproducible,
+ * independent of n.                                                                                                             */
+int ndp_pyramid_jac(const ndp_layer_desc *desc, int m, int k0, const float *params_all, int p_stride, int min_level, int max_level,
+                    const float *x, int n, float *x_out, float *J /*[n][9] row-major, J[3a+b] = dx'_a/dx_b*/,
+                    const float *normals_in /*may be NULL*/, float *normals_out /*may be NULL*/, void *stream);
+
+/* The inverse warp: Newton on W(x) = y with W the warp of levels min_level..max_level, every iteration of a 64-point tile inside ONE
+ * launch (tiles are independent: no grid-wide synchronisation, no host round trip).
+ *   y [n][3] targets; x [n][3] in: first guess (e.g. a copy of y), out: solution.
+ *   Pass it = 0, 1, ..: evaluate W(x) and J; a point with max |W(x) - y| <= tol is frozen; otherwise, while it < iters, it steps
+ *   x <- x - J^-1 (W(x) - y) (closed-form 3 x 3 solve through the cofactor matrix); at most `iters` steps, iters + 1 evaluations.
+ *   residual [n]: max |W(x) - y| of the x written (the W of ndp_pyramid_fwd: a caller who recomputes it gets the same float);
+ *   status [n] int: the number of steps taken when converged (0: the first guess already met tol and x is unchanged), -1 not
+ *   converged within iters, -2 stopped on non-finite values or |det J| < 1e-12 (x is the last point evaluated).
+ * No line search or trust region: where the field folds (det J <= 0 nearby) Newton may diverge, and the status says so.
+ * Refusals as ndp_pyramid_jac, plus iters < 1 and tol not positive and finite.                                                   */
+int ndp_pyramid_inverse(const ndp_layer_desc *desc, int m, int k0, const float *params_all, int p_stride, int min_level, int max_level,
+                        const float *y, int n, float *x /*in: first guess, out: solution*/, int iters, float tol,
+                        float *residual /*[n]*/, int *status /*[n] int*/, void *stream);
+
 /* Per-cloud means (registration.py:150-153: src_pcd.mean(dim=0), tgt_pcd.mean(dim=0)); means[0..2] = source,
  * means[4..6] = target (means[3], means[7] = 0).  Accumulated in double in a fixed order, rounded once.   */
 int ndp_pair_means(const float *src, int n_src, const float *tgt, int n_tgt, float *means, void *stream);

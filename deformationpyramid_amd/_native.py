@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libndp_hip.so")
 SOURCES = ["ndp_kernels.hip"]
-HEADERS = ["ndp_device.h", "ndp_nerfies.inc", "ndp_ed.inc", "ndp_fwd_split.inc", "ndp_bwd_split.inc", "ndp_bwd_fused.inc", "ndp_nn_matrix.inc", "ndp_generic.inc", "ndp_jacobian.inc", os.path.join("..", "..", "include", "ndp_hip.h"), os.path.join("..", "..", "include", "ndp_types.h")]
+HEADERS = ["ndp_device.h", "ndp_nerfies.inc", "ndp_ed.inc", "ndp_fwd_split.inc", "ndp_bwd_split.inc", "ndp_bwd_fused.inc", "ndp_nn_matrix.inc", "ndp_nn_cells.inc", "ndp_generic.inc", "ndp_jacobian.inc", os.path.join("..", "..", "include", "ndp_hip.h"), os.path.join("..", "..", "include", "ndp_types.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-pass-failed"]
 
 NDP_MAX_LEVELS = 16
@@ -59,7 +59,9 @@ class Engine(ctypes.Structure):
                 ("d2x", ctypes.c_void_p), ("idx_x", ctypes.c_void_p), ("d2y", ctypes.c_void_p),
                 ("idx_y", ctypes.c_void_p), ("adam_tab", ctypes.c_void_p), ("dO", ctypes.c_void_p),
                 ("nn_row", ctypes.c_void_p), ("nn_mode", ctypes.c_int), ("gemm_mode", ctypes.c_int),
-                ("gmax", ctypes.c_void_p)]
+                ("gmax", ctypes.c_void_p),
+                ("nn_cells", ctypes.c_int), ("pad_i", ctypes.c_int),
+                ("nnc_geom", ctypes.c_void_p), ("nnc_start", ctypes.c_void_p), ("nnc_rec", ctypes.c_void_p)]
 
 
 class WarpJob(ctypes.Structure):
@@ -78,6 +80,7 @@ class LoadJob(ctypes.Structure):
 MAX_WARP_JOBS = 32
 TICK_KERNELS = ("k_eng_fwd", "k_eng_nn", "k_eng_loss", "k_eng_bwd2", "k_eng_bwd1", "k_eng_update")   # one tick, launch order
 MAX_LOAD_JOBS = 16
+NNC_START = 4104                     # NDP_NNC_START: ints per cell_start table of the cell search
 
 
 def source_id():
@@ -168,6 +171,9 @@ _SIGS = {
     "ndp_chamfer_nn_matrix": [V, I, V, I, V, V, V, V, V, V],
     "ndp_engine_nn_matrix_fits": [I],
     "ndp_engine_nn_onepass_fits": [I],
+    "ndp_chamfer_nn_cells": [V, I, V, I, V, V, V, V, V, V, V, V],
+    "ndp_chamfer_nn_cells_workspace": [I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_engine_nn_cells_fits": [I, I],
     "ndp_chamfer_l1_bwd": [V, I, V, I, F, V, V, V, V, V, V, I, V],
     "ndp_flow_metrics": [V, V, V, I, V, V],
     "ndp_landmark_mse_fwd_bwd": [V, V, I, V, V, V],

@@ -1751,7 +1751,7 @@ __device__ __forceinline__ void eng_loss_body(const ndp_engine &e, int parity, i
     const int *idx_y = e.idx_y + (size_t)b * e.t_cap;
     // nearest target of a source: folded here from the one-pass kernel's per-chunk partials (nn_row_fold)
     const NnPart *rowpart = reinterpret_cast<const NnPart *>(e.nn_row) + (size_t)b * nn1_row_chunks(e.t_cap) * e.n_cap;
-    const bool rows_final = e.nn_mode == 1;          // latency shape: d2x / idx_x already hold the answer
+    const bool rows_final = e.nn_mode == 1 || e.nn_cells != 0;       // latency shape / cell search: d2x / idx_x already hold the answer
     const int rows_cstep = eng_nn_mx8(e) ? 2 : 1;    // the 8-wave matrix-pipe kernel leaves one partial per 512 targets
     const bool use_cd = gm.S > 0 && e.w_cd != 0.f;
     const HeadCfg hcl = make_head_cfg(desc_at_level(e.desc, st.level));
@@ -2403,6 +2403,8 @@ k_eng_load(ndp_engine e, int parity, LoadJobs jobs) {
     }
 }
 
+#include "ndp_nn_cells.inc"            // (behind LoadJobs: its grid-build kernel rides behind k_eng_load)
+
 // ------------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ------------------------------------------------------------------------------------------------
@@ -2454,7 +2456,7 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 #ifndef NDP_BUILD_ID
 #define NDP_BUILD_ID "unversioned"
 #endif
-extern "C" int ndp_version(void) { return 206; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written; 204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]; 205: ndp_level_bwd gained the trailing `dx` (dL/dx of the level's input points, may be NULL); 206: ndp_pyramid_jac, ndp_pyramid_inverse
+extern "C" int ndp_version(void) { return 207; }           // 201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out; 202: h2 as a plane image under gemm_mode 7; 203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written; 204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]; 205: ndp_level_bwd gained the trailing `dx` (dL/dx of the level's input points, may be NULL); 206: ndp_pyramid_jac, ndp_pyramid_inverse; 207: ndp_engine gained nn_cells and its grid buffers, ndp_chamfer_nn_cells
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }
@@ -2652,6 +2654,19 @@ static int check_engine(const ndp_engine *e, const char *who) {
     return 0;
 }
 
+static int check_nn_cells(const ndp_engine *e, const char *who) {
+    if (!nnc_fits(e->n_cap, e->t_cap)) {
+        snprintf(g_err, sizeof g_err, "%s: nn_cells needs n_cap and t_cap <= %d (ndp_engine_nn_cells_fits)", who, NNC_MAX);
+        return NDP_E_UNSUPPORTED;
+    }
+    if (!e->nnc_geom || !e->nnc_start || !e->nnc_rec || !aligned16(e->nnc_start) || !aligned16(e->nnc_rec)) {
+        snprintf(g_err, sizeof g_err, "%s: nn_cells without its grid buffers (nnc_geom, nnc_start, nnc_rec; 16-byte aligned)", who);
+        return NDP_E_INVALID;
+    }
+    if (int rc = set_smem((const void *)k_eng_nn_cells_build, NNC_LDS_BYTES)) return rc;
+    return set_smem((const void *)k_eng_nn_cells, NNC_LDS_BYTES);
+}
+
 extern "C" int ndp_engine_load(const ndp_engine *e, int tick, const ndp_load_job *jobs, int n_jobs, void *stream) {
     if (int rc = check_engine(e, "ndp_engine_load")) return rc;
     if (n_jobs < 0 || n_jobs > NDP_MAX_LOAD_JOBS || (n_jobs > 0 && !jobs)) return fail(NDP_E_INVALID, "ndp_engine_load: bad job count");
@@ -2682,6 +2697,11 @@ extern "C" int ndp_engine_load(const ndp_engine *e, int tick, const ndp_load_job
     }
     hipLaunchKernelGGL(k_eng_load, dim3(32, n_jobs), dim3(256), 0, (hipStream_t)stream, *e, tick & 1, lj);
     HIP_TRY(hipGetLastError(), "k_eng_load launch");
+    if (e->nn_cells && e->w_cd != 0.f && e->t_cap > 0) {          // the grid of the new pairs' targets: they stay put while the pair lives
+        if (int rc = check_nn_cells(e, "ndp_engine_load")) return rc;
+        hipLaunchKernelGGL(k_eng_nn_cells_build, dim3(n_jobs), dim3(NNC_NT), NNC_LDS_BYTES, (hipStream_t)stream, *e, lj);
+        HIP_TRY(hipGetLastError(), "k_eng_nn_cells_build launch");
+    }
     return 0;
 }
 
@@ -2813,6 +2833,8 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         if (int rc = set_smem((const void *)k_eng_nn_mx, nn2_lds_floats(e->n_cap) * 4)) return rc;
         if (nn2_lds_floats(e->n_cap, 8) * 4 <= 160 * 1024) if (int rc = set_smem((const void *)k_eng_nn_mx8, nn2_lds_floats(e->n_cap, 8) * 4)) return rc;
     }
+    const bool nn_cells = nn && e->nn_cells != 0;                  // the cell search takes the NN stage's slot, whatever nn_mode names
+    if (nn_cells) if (int rc = check_nn_cells(e, "ndp_engine_run")) return rc;
     // the matrix-pipe kernel in its 8-wave shape (512 targets per workgroup) where its LDS table fits
     const bool nn_mx8 = eng_nn_mx8(*e);
     const dim3 blk(256);
@@ -2852,6 +2874,7 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         else hipLaunchKernelGGL(k_eng_fwd, g_lvl, blk, kSmemFwdBytes, s, *e, parity);
         NDP_EV();
         if (!NDP_ST(1)) {}
+        else if (nn_cells) hipLaunchKernelGGL(k_eng_nn_cells, dim3(2, e->B), dim3(NNC_NT), NNC_LDS_BYTES, s, *e, parity);
         else if (nn && e->nn_mode == 1 && e->B <= 2) hipLaunchKernelGGL(k_eng_nn_lat16, g_nn_lat, dim3(1024), (3 * NN_STAGE + 2 * 1024) * 4, s, *e, parity);
         else if (nn && e->nn_mode == 1) hipLaunchKernelGGL(k_eng_nn_lat8, g_nn_lat, dim3(512), (3 * NN_STAGE + 2 * 512) * 4, s, *e, parity);
         else if (nn_mx8) hipLaunchKernelGGL(k_eng_nn_mx8, dim3((e->t_cap + 511) / 512, e->B), dim3(512), nn2_lds_floats(e->n_cap, 8) * 4, s, *e, parity);
@@ -2919,6 +2942,26 @@ extern "C" int ndp_chamfer_nn_matrix(const float *x, int S, const float *y, int 
     return 0;
 }
 extern "C" int ndp_engine_nn_matrix_fits(int n_cap) { return nn2_fits(n_cap) ? 1 : 0; }
+
+extern "C" int ndp_engine_nn_cells_fits(int n_cap, int t_cap) { return nnc_fits(n_cap, t_cap) ? 1 : 0; }
+extern "C" int ndp_chamfer_nn_cells_workspace(int T, long long *floats) {
+    if (T < 0 || !floats) return fail(NDP_E_INVALID, "ndp_chamfer_nn_cells_workspace: bad arguments");
+    *floats = nnc_ws_floats(T);
+    return 0;
+}
+extern "C" int ndp_chamfer_nn_cells(const float *x, int S, const float *y, int T, const int *prev_idx_x, const int *prev_idx_y,
+                                    float *d2x, int *idx_x, float *d2y, int *idx_y, float *workspace, void *stream) {
+    if (S <= 0 || T <= 0 || !x || !y || !d2x || !idx_x || !d2y || !idx_y || !workspace || !aligned16(workspace))
+        return fail(NDP_E_INVALID, "ndp_chamfer_nn_cells: bad arguments (the workspace must be 16-byte aligned)");
+    if (!nnc_fits(S, T)) return fail(NDP_E_UNSUPPORTED, "ndp_chamfer_nn_cells: S and T must be <= 2048 (ndp_engine_nn_cells_fits)");
+    if (int rc = set_smem((const void *)k_nn_cells_build, NNC_LDS_BYTES)) return rc;
+    if (int rc = set_smem((const void *)k_nn_cells, NNC_LDS_BYTES)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_nn_cells_build, dim3(1), dim3(NNC_NT), NNC_LDS_BYTES, s, y, T, workspace);
+    hipLaunchKernelGGL(k_nn_cells, dim3(2), dim3(NNC_NT), NNC_LDS_BYTES, s, x, S, y, T, prev_idx_x, prev_idx_y, d2x, idx_x, d2y, idx_y, workspace);
+    HIP_TRY(hipGetLastError(), "k_nn_cells launch");
+    return 0;
+}
 extern "C" int ndp_engine_nn_onepass_fits(int n_cap) { return nn1_lds_floats(n_cap, nn1_stage_x(n_cap)) * 4 <= 160 * 1024 ? 1 : 0; }
 
 extern "C" int ndp_engine_run(const ndp_engine *e, int tick0, int n_ticks, void *stream) {

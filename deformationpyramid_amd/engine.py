@@ -47,6 +47,9 @@ class OptConfig:
 #   nn matrix : the one-pass NN with the distances on the bf16 matrix pipe and exact re-evaluation (bit-identical results).
 DEFAULT_GEMM_MODE = 7
 DEFAULT_NN_MATRIX = True
+#   nn cells  : the NN stage as an exact grid ball search seeded by last tick's neighbours (bit-identical results) wherever the engine
+#               itself chose a one-pass shape and n_cap, t_cap <= 2048; nn_mode still names the dense kernel it replaces.
+DEFAULT_NN_CELLS = True
 # every bit gemm_mode may carry (ndp_hip.h); bits 64, 128, 256 and 512 selected measured variants until ABI 204 and are refused
 GEMM_MODE_BITS = 1 | 2 | 4 | 8 | 16 | 32 | 1024
 
@@ -84,6 +87,20 @@ def resolve_modes(B, n_cap, t_cap, gemm_mode=None, nn_mode=None, nn_matrix=None)
     return gemm_mode, want
 
 
+def resolve_nn_cells(n_cap, t_cap, nn_mode_given, nn_mode, nn_cells=None):
+    """-> whether the engine's nearest-neighbour stage is the exact grid ball search (csrc/ndp_nn_cells.inc) instead of the dense
+    kernel its nn_mode names.  None: on where the engine itself chose a one-pass shape (no nn_mode given, nn_mode 0 or 2) and the
+    capacities fit (ndp_engine_nn_cells_fits: both <= 2048); an explicit nn_mode keeps that shape running.  True with capacities that
+    do not fit raises."""
+    fits = bool(N.lib().ndp_engine_nn_cells_fits(n_cap, t_cap))
+    if nn_cells is None:
+        return DEFAULT_NN_CELLS and nn_mode_given is None and nn_mode != 1 and fits
+    if nn_cells and not fits:
+        raise N.NdpError(f"nn_cells: n_cap = {n_cap}, t_cap = {t_cap} do not fit the cell search (ndp_engine_nn_cells_fits: both <= 2048); "
+                         "leave nn_cells unset and the engine keeps its dense kernel")
+    return bool(nn_cells)
+
+
 class Snapshot:
     """Host copy of the [B] pair states of one tick."""
     __slots__ = ("raw", "sz", "level")
@@ -100,7 +117,7 @@ class Snapshot:
 
 
 class BatchedEngine:
-    def __init__(self, desc: LayerDesc, cfg: OptConfig, B: int, n_cap: int, t_cap: int, device, G=None, nn_mode=None, gemm_mode=None, nn_matrix=None):
+    def __init__(self, desc: LayerDesc, cfg: OptConfig, B: int, n_cap: int, t_cap: int, device, G=None, nn_mode=None, gemm_mode=None, nn_matrix=None, nn_cells=None):
         # desc.nonrigidity = True means "every level but the first carries the gate" (nets.py:26); P is then the
         # parameter count of a gated level and level 0 uses a prefix-compatible shorter layout.
         self.lib = N.lib()
@@ -108,6 +125,7 @@ class BatchedEngine:
         self.n_cap, self.t_cap = cap(n_cap), cap(t_cap)
         # modes are resolved and validated HERE, once (see resolve_modes): nothing later reads the environment
         self.gemm_mode, self.nn_mode = resolve_modes(B, self.n_cap, self.t_cap, gemm_mode, nn_mode, nn_matrix)
+        self.nn_cells = resolve_nn_cells(self.n_cap, self.t_cap, nn_mode, self.nn_mode, nn_cells)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise N.NdpError("BatchedEngine needs a GPU device; there is no CPU fallback")
@@ -140,6 +158,10 @@ class BatchedEngine:
         nr = ctypes.c_longlong()
         N.check(self.lib.ndp_engine_nn_workspace(self.n_cap, self.t_cap, ctypes.byref(nr)), "ndp_engine_nn_workspace")
         self.nn_row = torch.zeros(B, max(nr.value, 1), **f32)   # one-pass 1-NN row partials ({d2, idx} per source and target chunk)
+        if self.nn_cells:                # the targets' grid per slot: geometry, cell_start, records sorted by cell (ndp_engine_load builds it)
+            self.nnc_geom = torch.zeros(B, 8, **f32)
+            self.nnc_start = torch.zeros(B, N.NNC_START, device=d, dtype=torch.int32)
+            self.nnc_rec = torch.zeros(B, self.t_cap, 4, **f32)
         tab = np.zeros((cfg.iters + 1, 2), dtype=np.float32)
         for t in range(1, cfg.iters + 1):
             tab[t] = adam_scalars(t, cfg.lr)
@@ -170,6 +192,10 @@ class BatchedEngine:
         for name in ("geom", "state", "pts", "ldmk_t", "tgt", "params", "gpart", "adam_m", "adam_v", "act", "heads",
                      "d2x", "idx_x", "d2y", "idx_y", "adam_tab", "dO", "nn_row", "gmax"):
             setattr(e, name, getattr(self, name).data_ptr())
+        e.nn_cells = int(self.nn_cells)
+        if self.nn_cells:
+            for name in ("nnc_geom", "nnc_start", "nnc_rec"):
+                setattr(e, name, getattr(self, name).data_ptr())
         self.c_engine = e
 
     # ------------------------------------------------------------------ slot management

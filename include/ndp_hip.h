@@ -212,6 +212,20 @@ int ndp_engine_nn_matrix_fits(int n_cap);
  * beyond that an engine must use nn_mode 1 (latency shape: no table, no size limit).                                                 */
 int ndp_engine_nn_onepass_fits(int n_cap);
 
+/* The same result from an exact grid ball search (what an engine with nn_cells runs every tick): the references of each direction are
+ * sorted into a 16^3 grid over the TARGETS' bounding box; a query evaluates, with the brute force's own fma chain, only the references in
+ * the cells that the ball around it touches -- radius = its exact distance to a seed reference, widened by an explicit rounding margin
+ * (csrc/ndp_nn_cells.inc) -- and keeps the smallest distance with the lowest index.  Bit-identical to ndp_chamfer_nn_fwd for ANY seeds.
+ *   prev_idx_x [S] / prev_idx_y [T] (either may be NULL): seed indices, e.g. the previous call's idx_x / idx_y; an entry that is
+ *   negative or not below the reference count is ignored (the seed then comes from the nearest non-empty cells).  They may alias
+ *   idx_x / idx_y.   workspace: ndp_chamfer_nn_cells_workspace(T) floats, 16-byte aligned.
+ * S, T <= 2048 (ndp_engine_nn_cells_fits); beyond that NDP_E_UNSUPPORTED.                                                           */
+int ndp_chamfer_nn_cells(const float *x, int S, const float *y, int T, const int *prev_idx_x, const int *prev_idx_y,
+                         float *d2x, int *idx_x, float *d2y, int *idx_y, float *workspace, void *stream);
+int ndp_chamfer_nn_cells_workspace(int T, long long *floats);
+/* 1 when an engine of these capacities can search by cells (ndp_engine.nn_cells): both <= 2048. */
+int ndp_engine_nn_cells_fits(int n_cap, int t_cap);
+
 /* Truncated L1 Chamfer value and gradient from the NN result (loss.py:185-258 and its autograd):
  * loss[0] = sum_i sqrt(d2x_i)[d2x_i<trunc]/S + sum_j sqrt(d2y_j)[d2y_j<trunc]/T   (point_sum != 0: without the /S, /T --
  * point_reduction="sum", loss.py:233-235) ;
@@ -323,7 +337,15 @@ typedef struct ndp_engine {
     unsigned int *gmax;              /* [B] bit pattern of max |dO| of the pair this tick (zeroed by the forward stage, raised by
                                         the loss stage): the power-of-two scale that puts the split backward's gradient operands
                                         into fp16's range.  Required when gemm_mode & 6, else may be NULL.                       */
+    int nn_cells, pad_i;             /* ABI 207.  nn_cells != 0: the nearest-neighbour stage is the exact grid ball search
+                                        (csrc/ndp_nn_cells.inc: k_eng_nn_cells, bit-identical results, needs
+                                        ndp_engine_nn_cells_fits(n_cap, t_cap)) in place of the dense kernel nn_mode names; nn_mode
+                                        keeps its value and meaning.  ndp_engine_load then also builds the grid of a slot's targets. */
+    float *nnc_geom;                 /* [B][8] grid geometry per pair: origin[3], cells per unit length[3], 2 pad (NULL without nn_cells) */
+    int *nnc_start;                  /* [B][NDP_NNC_START] cell_start of the targets' grid, x fastest (NULL without nn_cells)            */
+    float *nnc_rec;                  /* [B][t_cap][4] the targets sorted by cell: {x, y, z, index bits}, 16-byte aligned (NULL without)   */
 } ndp_engine;
+#define NDP_NNC_START 4104           /* ints per cell_start table: 16^3 + 1 entries, padded to a multiple of 4 */
 
 /* Floats PER PAIR of the row-partial buffer of the one-pass nearest-neighbour kernel ({d2, idx} per source and
  * 128-target chunk).                                                                                             */

@@ -1,4 +1,4 @@
-"""Engine modes for the measurement tools: NDP_GEMM_MODE / NDP_NN_MODE in the environment -> Registration / BatchedEngine
+"""Engine modes for the measurement tools: NDP_GEMM_MODE / NDP_NN_MODE / NDP_NN_CELLS (0 / 1) in the environment -> Registration / BatchedEngine
 keyword arguments.  (The package itself reads no environment variable: modes are constructor arguments.)"""
 import os
 
@@ -16,4 +16,6 @@ def from_env():
         if nn not in (0, 1, 2):
             raise SystemExit(f"NDP_NN_MODE must be 0, 1 or 2, got {nn}")
         kw["nn_mode"] = nn
+    if os.environ.get("NDP_NN_CELLS"):
+        kw["nn_cells"] = bool(int(os.environ["NDP_NN_CELLS"]))
     return kw

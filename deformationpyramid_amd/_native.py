@@ -43,6 +43,10 @@ class PairState(ctypes.Structure):
                 ("loss_prev", ctypes.c_double), ("evals_per_level", ctypes.c_int * NDP_MAX_LEVELS)]
 
 
+# PairState.decision (the NDP_DEC_* enum of include/ndp_hip.h)
+DEC_STEP, DEC_ADVANCE, DEC_STEP_ADVANCE, DEC_IDLE = 0, 1, 2, 3
+
+
 class Engine(ctypes.Structure):
     _fields_ = [("desc", CLayerDesc), ("m", ctypes.c_int), ("k0", ctypes.c_int),
                 ("P", ctypes.c_int), ("p_stride", ctypes.c_int),

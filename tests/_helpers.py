@@ -74,6 +74,16 @@ def registration_modes(arith):
     return dict(gemm_mode=7, nn_matrix=True) if arith == "split" else dict(gemm_mode=0, nn_matrix=False)
 
 
+# Slot-history tests (tests/test_slot_history.py): every device buffer the engine hands to the kernels through the C struct
+# (the pointer-typed fields of _native.Engine) is either overwritten with garbage before a pair is loaded -- the pair's bits
+# must not notice -- or exempt for a stated reason.  tests/test_slot_history_cpu.py keeps the two lists complete.
+ENGINE_POISONED = ("geom", "state", "pts", "ldmk_t", "tgt", "params", "gpart", "adam_m", "adam_v", "act", "heads",
+                   "d2x", "idx_x", "d2y", "idx_y", "dO", "nn_row", "gmax", "nnc_geom", "nnc_start", "nnc_rec")
+ENGINE_POISON_EXEMPT = {
+    "adam_tab": "constant table of Adam's step scalars: filled by the constructor, read-only for every kernel, not per slot",
+}
+
+
 # width / depth other than the shipped 128 / 3 (fixture F16, tests/golden/make_golden.py: F16_SHAPES)
 GENERIC_SHAPES = {
     "w64d2_se3aa": dict(width=64, depth=2, rotation_format="axis_angle", motion="SE3"),

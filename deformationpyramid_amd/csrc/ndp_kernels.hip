@@ -1858,7 +1858,9 @@ __device__ __forceinline__ void eng_loss_body(const ndp_engine &e, int parity, i
     const int i_self = p - gm.K;                     // sample index (negative for landmarks)
     // Every phase below is a chain of 1-2 us global round trips (tools/phase_timing.py), so what can be requested now is: the
     // chunk's nearest-source indices (local point of target c0 + t + 256 k, -1: not ours) travel with the row partials.
-    const bool scatter = use_cd && vb * 256 + 255 >= gm.K;      // workgroup holds at least one sample
+    // workgroup holds at least one sample AND there is a target to scatter (T == 0: the chunk loop below would never run, and with it
+    // the head rows would never reach LDS -- ndp_engine_load refuses such a pair, this keeps a state written around it defined)
+    const bool scatter = use_cd && gm.T > 0 && vb * 256 + 255 >= gm.K;
     const int i_lo = vb * 256 - gm.K;                      // sample index of thread 0
     // (UNCONDITIONAL loads at a clamped index -- idx_y is padded with -1 up to t_cap: as `cond ? idx_y[j] : -1` every one of the eight
     //  became a branch around a load with its own wait, eight dependent global round trips at the top of every gradient workgroup,
@@ -2684,6 +2686,8 @@ extern "C" int ndp_engine_load(const ndp_engine *e, int tick, const ndp_load_job
                 (q.K > 0 && !e->ldmk_t))
                 return fail(NDP_E_INVALID, "ndp_engine_load: null cloud pointer");
             if (!aligned16(q.params)) return fail(NDP_E_INVALID, "ndp_engine_load: params must be 16-byte aligned");
+            if (q.S > 0 && q.T == 0 && e->w_cd != 0.f)
+                return fail(NDP_E_INVALID, "ndp_engine_load: samples without targets (S > 0, T == 0) under a Chamfer term (w_cd != 0): the loss would be 0/0");
         }
         if (q.params && q.n_src > 0) {
             if (!q.means || !q.src || !q.tgt || q.n_tgt < 1) return fail(NDP_E_INVALID, "ndp_engine_load: means to compute need src, tgt, n_tgt and the means buffer");

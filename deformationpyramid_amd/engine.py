@@ -222,6 +222,9 @@ class BatchedEngine:
                 K, S, T = int(j["K"]), int(j["S"]), int(j.get("T", 0))
                 if K + S > self.n_cap or T > self.t_cap or K + S < 1:
                     raise ValueError(f"pair does not fit the engine capacities: n={K + S}/{self.n_cap}, T={T}/{self.t_cap}")
+                if S > 0 and T == 0 and self.c_engine.w_cd != 0.0:
+                    raise ValueError(f"pair has {S} samples and no target under a Chamfer term (w_cd = {self.cfg.w_cd}): the loss would "
+                                     "be 0/0; give it targets, or load its landmarks alone (S = 0)")
                 q.params, q.K, q.S, q.T = params.data_ptr(), K, S, T
                 q.src, q.tgt = ptr(j.get("src")), ptr(j.get("tgt"))
                 q.perm_s, q.perm_t = ptr(j.get("perm_s")), ptr(j.get("perm_t"))

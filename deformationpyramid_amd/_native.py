@@ -4,7 +4,9 @@ There is deliberately NO fallback: if the HIP library is missing or an entry poi
 caller gets an exception.  `build()` compiles the library in-tree with hipcc for gfx950.
 """
 import ctypes
+import hashlib
 import os
+import re
 import shutil
 import subprocess
 
@@ -14,8 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libndp_hip.so")
-SOURCES = ["ndp_kernels.hip"]
-HEADERS = ["ndp_device.h", "ndp_nerfies.inc", "ndp_ed.inc", "ndp_fwd_split.inc", "ndp_bwd_split.inc", "ndp_bwd_fused.inc", "ndp_nn_matrix.inc", "ndp_nn_cells.inc", "ndp_generic.inc", "ndp_jacobian.inc", os.path.join("..", "..", "include", "ndp_hip.h"), os.path.join("..", "..", "include", "ndp_types.h")]
+SOURCES = ["ndp_kernels.hip"]                        # the one translation unit; what it includes is found by _closure()
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-pass-failed"]
 
 NDP_MAX_LEVELS = 16
@@ -87,26 +88,36 @@ MAX_LOAD_JOBS = 16
 NNC_START = 4104                     # NDP_NNC_START: ints per cell_start table of the cell search
 
 
-def source_id():
-    """Hex digest of the sources the library is built from (kernel file, device header, the two ABI headers) and of
-    the compile flags.  It is compiled into the library (-DNDP_BUILD_ID) and returned by ndp_build_id(): a library
-    whose id differs from the tree's was built from other sources -- lib() rebuilds it or refuses to load it, because
-    ndp_engine / ndp_load_job are passed BY VALUE into kernels and a stale layout would corrupt device memory."""
-    import hashlib
+def _closure(sources):
+    """{path: bytes} of everything the compiler reads for `sources` (names under CSRC): the sources, then every `#include "..."` reached
+    from them, resolved relative to the including file as the compiler does -- depth first in include order, each file once."""
+    seen = {}
+    def visit(path):
+        path = os.path.normpath(path)
+        if path not in seen:
+            with open(path, "rb") as f:
+                seen[path] = f.read()
+            for inc in re.findall(rb'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', seen[path], re.M):
+                visit(os.path.join(os.path.dirname(path), inc.decode()))
+    for s in sources:
+        visit(os.path.join(CSRC, s))
+    return seen
+
+
+def _tree_id(sources, flags):
+    """Hex digest of _closure(sources) and of the compile flags, or None in a deployment without csrc/ (the prebuilt library's
+    embedded id stands then, see _is_stale).  An #include that names no file is an error, not such a deployment."""
+    if not os.path.exists(os.path.join(CSRC, sources[0])):
+        return None
     h = hashlib.sha256()
-    try:
-        for d in [os.path.join(CSRC, s) for s in SOURCES] + [os.path.normpath(os.path.join(CSRC, x)) for x in HEADERS]:
-            with open(d, "rb") as f:
-                h.update(f.read())
-    except OSError:
-        return None                      # a deployment without csrc/: the prebuilt library's embedded id stands (see _stale)
-    h.update(" ".join(HIPCC_FLAGS).encode())
+    for text in _closure(sources).values():
+        h.update(text)
+    h.update(" ".join(flags).encode())
     return h.hexdigest()[:16]
 
 
 def _built_id(path, tag=b"NDP_BUILD_ID"):
     """Build id of an existing library file (the tag string ndp_build_id() returns, found without loading it), or None."""
-    import re
     try:
         with open(path, "rb") as f:
             hit = re.search(tag + rb"=([0-9a-f]{16})", f.read())
@@ -115,35 +126,56 @@ def _built_id(path, tag=b"NDP_BUILD_ID"):
         return None
 
 
-def _stale():
-    sid = source_id()
-    if sid is None:                      # no sources to compare with: any library that carries an id is taken as built
-        return _built_id(LIBPATH) is None
-    return not os.path.exists(LIBPATH) or _built_id(LIBPATH) != sid
+def _is_stale(path, tag, tree_id):
+    built = _built_id(path, tag)         # None: no such file, or it carries no id
+    return built is None if tree_id is None else built != tree_id       # no sources to compare with: any library with an id is taken as built
 
 
-def build(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 ... -> deformationpyramid_amd/lib/libndp_hip.so (in-tree).  Serialised by a file
-    lock: N ranks that find a stale library build it once."""
+def _build(path, tag, macro, sources, flags, compilers, lock, force, verbose=False):
+    """Compile `sources` into `path` (in-tree) unless the id it carries is the tree's.  Serialised by a file lock with the staleness
+    re-checked under it: N ranks that find a stale library build it once."""
     import fcntl
+    tree_id = _tree_id(sources, flags)
+    if not force and not _is_stale(path, tag, tree_id):
+        return path
     os.makedirs(LIBDIR, exist_ok=True)
-    with open(os.path.join(LIBDIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if not force and not _stale():
-            return LIBPATH
-        if source_id() is None:
-            raise NdpError(f"{LIBPATH} is missing (or carries no build id) and this deployment has no csrc/ to build it from: "
+    with open(os.path.join(LIBDIR, lock), "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not force and not _is_stale(path, tag, tree_id):
+            return path
+        if tree_id is None:
+            raise NdpError(f"{path} is missing (or carries no build id) and this deployment has no csrc/ to build it from: "
                            "ship the prebuilt library with the package (its layout is checked against the Python structs by ndp_abi_sizes)")
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        if not os.path.exists(hipcc):
-            raise NdpError("hipcc not found and libndp_hip.so is missing or stale")
-        tmp = f"{LIBPATH}.{os.getpid()}.tmp"          # build aside + atomic rename: nobody ever sees a torn file
-        cmd = [hipcc] + HIPCC_FLAGS + [f'-DNDP_BUILD_ID="{source_id()}"', "-o", tmp] + [os.path.join(CSRC, s) for s in SOURCES]
+        cc = next((c for c in (shutil.which(compilers[0]),) + compilers[1:] if c and os.path.exists(c)), None)
+        if cc is None:
+            raise NdpError(f"{compilers[0]} not found and {os.path.basename(path)} is missing or stale")
+        tmp = f"{path}.{os.getpid()}.tmp"             # build aside + atomic rename: nobody ever sees a torn file
+        cmd = [cc] + flags + [f'-D{macro}="{tree_id}"', "-o", tmp] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-        os.replace(tmp, LIBPATH)
-    return LIBPATH
+        os.replace(tmp, path)
+    return path
+
+
+def source_id():
+    """Digest of everything libndp_hip.so is compiled from and of the compile flags, compiled into the library (-DNDP_BUILD_ID) and
+    returned by ndp_build_id(): a library whose id differs from the tree's was built from other sources -- lib() rebuilds it or refuses
+    to load it, because ndp_engine / ndp_load_job are passed BY VALUE into kernels and a stale layout would corrupt device memory."""
+    return _tree_id(SOURCES, HIPCC_FLAGS)
+
+
+# what SOURCES include, relative to CSRC ("ndp_device.h", "ndp_nn_cells.inc", "../../include/ndp_hip.h", ...): computed, for readers
+HEADERS = [os.path.relpath(p, CSRC) for p in list(_closure(SOURCES))[len(SOURCES):]] if os.path.isdir(CSRC) else []
+
+
+def _stale():
+    return _is_stale(LIBPATH, b"NDP_BUILD_ID", source_id())
+
+
+def build(force=False, verbose=False):
+    """hipcc --offload-arch=gfx950 ... -> deformationpyramid_amd/lib/libndp_hip.so (in-tree)."""
+    return _build(LIBPATH, b"NDP_BUILD_ID", "NDP_BUILD_ID", SOURCES, HIPCC_FLAGS, ("hipcc", "/opt/rocm/bin/hipcc"), ".build.lock", force, verbose)
 
 
 _LIB = None
@@ -246,7 +278,8 @@ def lib(allow_build=True):
 
 # ------------------------------------------------------------------ host runtime library (no GPU)
 HOST_LIBPATH = os.path.join(LIBDIR, "libndp_host.so")
-HOST_SOURCE = os.path.join(CSRC, "ndp_host.cpp")
+HOST_SOURCES = ["ndp_host.cpp", "ndp_graph.cpp"]                          # RNG replay; embedded-deformation graph builder
+HOST_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-mfma", "-mavx2", "-fPIC", "-shared"]
 _HOST = None
 
 
@@ -254,48 +287,14 @@ class DrawOp(ctypes.Structure):
     _fields_ = [("n", ctypes.c_longlong), ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("offset", ctypes.c_longlong)]
 
 
-HOST_SOURCES = [HOST_SOURCE, os.path.join(CSRC, "ndp_graph.cpp")]      # RNG replay; embedded-deformation graph builder
-
-
-HOST_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-mfma", "-mavx2", "-fPIC", "-shared"]
-
-
 def _host_id():
     """Digest of the host library's sources and flags (compiled in as NDP_HOST_BUILD_ID), or None without sources."""
-    import hashlib
-    h = hashlib.sha256()
-    try:
-        for src in HOST_SOURCES:
-            with open(src, "rb") as f:
-                h.update(f.read())
-    except OSError:
-        return None
-    h.update(" ".join(HOST_FLAGS).encode())
-    return h.hexdigest()[:16]
-
-
-def _host_stale():
-    hid = _host_id()
-    built = _built_id(HOST_LIBPATH, b"NDP_HOST_ID")
-    if hid is None:
-        return built is None
-    return built != hid
+    return _tree_id(HOST_SOURCES, HOST_FLAGS)
 
 
 def build_host(force=False):
-    """g++ -> deformationpyramid_amd/lib/libndp_host.so; rebuilt when the digest of its sources changes (the digest is
-    compiled into the library).  Serialised by a file lock, staleness re-checked under the lock: N ranks build once."""
-    if force or _host_stale():
-        import fcntl
-        os.makedirs(LIBDIR, exist_ok=True)
-        with open(os.path.join(LIBDIR, ".build_host.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            if not force and not _host_stale():
-                return HOST_LIBPATH
-            tmp = f"{HOST_LIBPATH}.{os.getpid()}.tmp"
-            subprocess.check_call(["g++"] + HOST_FLAGS + [f'-DNDP_HOST_BUILD_ID="{_host_id()}"', "-o", tmp] + HOST_SOURCES)
-            os.replace(tmp, HOST_LIBPATH)
-    return HOST_LIBPATH
+    """g++ -> deformationpyramid_amd/lib/libndp_host.so; rebuilt when the digest of its sources changes."""
+    return _build(HOST_LIBPATH, b"NDP_HOST_ID", "NDP_HOST_BUILD_ID", HOST_SOURCES, HOST_FLAGS, ("g++",), ".build_host.lock", force)
 
 
 def host_lib():
@@ -305,7 +304,7 @@ def host_lib():
             build_host()                                # no-op when the embedded digest matches
         if not os.path.exists(HOST_LIBPATH):
             raise NdpError(f"{HOST_LIBPATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        if _host_stale():                               # cannot be rebuilt here (no g++): refuse it, like the HIP library
+        if _is_stale(HOST_LIBPATH, b"NDP_HOST_ID", _host_id()):     # cannot be rebuilt here (no g++): refuse it, like the HIP library
             raise NdpError(f"{HOST_LIBPATH} was built from other sources (build id {_built_id(HOST_LIBPATH, b'NDP_HOST_ID')}, "
                            f"tree {_host_id()}): run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = ctypes.CDLL(HOST_LIBPATH)

@@ -1,0 +1,72 @@
+// ndp_abi_common.inc -- what every host entry uses (host-only): g_err / fail / hip_fail / HIP_TRY, check_desc, aligned16, set_smem;
+// and the entries about the library itself: ndp_version, ndp_last_error, ndp_build_id, ndp_abi_sizes.  Behind ndp_generic.inc
+// (check_desc asks gen_supported), ahead of the first file that carries host entries of its own.
+// ------------------------------------------------------------------------------------------------
+// host side of the C ABI
+// ------------------------------------------------------------------------------------------------
+static thread_local char g_err[256] = "";
+static int fail(int code, const char *msg) {
+    snprintf(g_err, sizeof g_err, "%s", msg);
+    return code;
+}
+static int hip_fail(hipError_t e, const char *what) {
+    snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
+    return (int)e;
+}
+#define HIP_TRY(expr, what)                                   \
+    do {                                                      \
+        hipError_t _e = (expr);                               \
+        if (_e != hipSuccess) return hip_fail(_e, what);      \
+    } while (0)
+
+static int check_desc(const ndp_layer_desc *d) {
+    if (!d) return fail(NDP_E_INVALID, "null layer descriptor");
+    if (gen_is_generic(*d) && !gen_supported(*d))                       // 128 / 3: the MFMA kernels; anything else: csrc/ndp_generic.inc
+        return fail(NDP_E_UNSUPPORTED, "width must be 1..256 and depth 1..4 (width=128, depth=3 run on the MFMA kernels, the rest on the generic fp32 kernels)");
+    if (d->motion < 0 || d->motion > 2) return fail(NDP_E_INVALID, "bad motion type");
+    if (d->motion != NDP_MOTION_SFLOW && (d->rotfmt < NDP_ROT_AXIS_ANGLE || d->rotfmt > NDP_ROT_6D))
+        return fail(NDP_E_INVALID, "bad rotation_format");
+    return 0;
+}
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+static int set_smem(const void *fn, int bytes) {
+    static thread_local const void *done[32];
+    for (auto d : done) if (d == fn) return 0;
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), "hipFuncSetAttribute");
+    for (auto &d : done) if (!d) { d = fn; break; }
+    return 0;
+}
+
+#ifdef NDP_PHASE_TIMING
+extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
+    if (hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 96) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[96] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof z) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
+
+#ifndef NDP_BUILD_ID
+#define NDP_BUILD_ID "unversioned"
+#endif
+// ABI versions:
+//   201: ndp_load_job gained n_src / n_tgt (88 bytes), `means` in/out
+//   202: h2 as a plane image under gemm_mode 7
+//   203: gemm_mode bits 512 / 1024, at G == 1 the matrix blocks of gpart are not written
+//   204: gemm_mode bits 64 / 128 / 256 / 512 refused, gmax is [B]
+//   205: ndp_level_bwd gained the trailing `dx` (dL/dx of the level's input points, may be NULL)
+//   206: ndp_pyramid_jac, ndp_pyramid_inverse
+//   207: ndp_engine gained nn_cells and its grid buffers, ndp_chamfer_nn_cells
+extern "C" int ndp_version(void) { return 207; }
+extern "C" const char *ndp_last_error(void) { return g_err; }
+static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
+extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }
+extern "C" int ndp_abi_sizes(int *out) {
+    if (!out) return fail(NDP_E_INVALID, "ndp_abi_sizes: null pointer");
+    out[0] = (int)sizeof(ndp_layer_desc); out[1] = (int)sizeof(ndp_pair_geom); out[2] = (int)sizeof(ndp_pair_state);
+    out[3] = (int)sizeof(ndp_engine);     out[4] = (int)sizeof(ndp_warp_job);  out[5] = (int)sizeof(ndp_load_job);
+    return 0;
+}

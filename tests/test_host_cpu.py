@@ -407,6 +407,63 @@ def test_stale_library_is_detected_by_its_build_id(tmp_path):
     assert L.ndp_abi_sizes(sizes) == 0 and sizes[3] == ctypes.sizeof(N.Engine) and sizes[2] == ctypes.sizeof(N.PairState)
 
 
+def test_build_id_covers_every_file_under_csrc_and_the_kernel_file_stays_a_spine():
+    """The hashed set is the include closure of the sources, so a file the compiler reads cannot be outside the digest; and no
+    *.inc / *.h lies under csrc/ that nothing includes.  ndp_kernels.hip itself holds the include list and no code."""
+    import glob
+    from deformationpyramid_amd import _native as N
+    hip, host = N._closure(N.SOURCES), N._closure(N.HOST_SOURCES)          # (a dangling #include "..." raises here)
+    assert all(os.path.isfile(p) and os.path.abspath(p).startswith(ROOT + os.sep) for p in list(hip) + list(host))
+    orphans = [p for p in glob.glob(os.path.join(N.CSRC, "*")) if p.endswith((".inc", ".h")) and os.path.normpath(p) not in hip]
+    assert not orphans, orphans
+    assert set(N.HEADERS) == {os.path.relpath(p, N.CSRC) for p in hip} - set(N.SOURCES) and "ndp_eng_loss.inc" in N.HEADERS
+    assert os.path.join("..", "..", "include", "ndp_types.h") in N.HEADERS                 # reached through ndp_device.h -> ndp_hip.h
+    assert len(glob.glob(os.path.join(N.CSRC, "*.inc"))) >= 22 and set(host) >= {os.path.join(N.CSRC, s) for s in N.HOST_SOURCES}
+    spine = open(os.path.join(N.CSRC, "ndp_kernels.hip")).read()
+    for word in ("__global__", "__device__", 'extern "C"'):
+        assert word not in spine, word
+
+
+def test_build_id_changes_with_every_file_of_the_include_closure(tmp_path, monkeypatch):
+    """One byte appended to any file the compiler reads changes the digest; so does the content of a file that is new to the tree
+    the moment something includes it -- for the HIP library and for the host library."""
+    import shutil
+    from deformationpyramid_amd import _native as N
+    pkg = tmp_path / "deformationpyramid_amd"
+    shutil.copytree(N.CSRC, pkg / "csrc")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    real = N.source_id(), N._host_id()
+    monkeypatch.setattr(N, "CSRC", str(pkg / "csrc"))
+    assert (N.source_id(), N._host_id()) == real                           # the digest does not depend on where the tree lies
+
+    def every_file_counts(tree_id, sources, includer):
+        seen = {tree_id()}
+        files = list(N._closure(sources))
+        assert all(p.startswith(str(tmp_path)) for p in files) and len(files) >= len(sources)
+        for p in files:
+            with open(p, "ab") as f:
+                f.write(b"\n")
+            seen.add(tree_id())
+        assert len(seen) == len(files) + 1, "a file of the closure is outside the digest"
+        (pkg / "csrc" / "ndp_new_stage.inc").write_text("// nothing yet\n")
+        before = tree_id()
+        assert before in seen                                              # not included: not read, not hashed
+        with open(pkg / "csrc" / includer, "a") as f:
+            f.write('#include "ndp_new_stage.inc"\n')
+        first = tree_id()
+        (pkg / "csrc" / "ndp_new_stage.inc").write_text("// nothing yet, but differently\n")
+        assert len({before, first, tree_id()}) == 3
+        (pkg / "csrc" / "ndp_new_stage.inc").unlink()
+        with pytest.raises(OSError):                                       # an #include that names no file is an error, not "no sources"
+            tree_id()
+
+    assert len(N._closure(N.SOURCES)) >= 26
+    every_file_counts(N.source_id, N.SOURCES, "ndp_eng_update.inc")
+    every_file_counts(N._host_id, N.HOST_SOURCES, "ndp_graph.cpp")
+    monkeypatch.setattr(N, "CSRC", str(tmp_path / "no_csrc"))               # a deployment without sources: no id, the library's stands
+    assert N.source_id() is None and N._host_id() is None
+
+
 def test_two_way_fp16_split_model_is_as_exact_as_fp32():
     """The arithmetic of the split level kernels (csrc/ndp_fwd_split.inc), modelled in numpy: x = hi + 2^-11 lo with hi = fp16(x),
     lo = fp16(2^11 (x - hi)) represents x to within 2^-23 |x| -- one fp32 ulp -- and a 128-term contraction from the

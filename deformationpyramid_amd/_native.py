@@ -66,7 +66,8 @@ class Engine(ctypes.Structure):
                 ("nn_row", ctypes.c_void_p), ("nn_mode", ctypes.c_int), ("gemm_mode", ctypes.c_int),
                 ("gmax", ctypes.c_void_p),
                 ("nn_cells", ctypes.c_int), ("pad_i", ctypes.c_int),
-                ("nnc_geom", ctypes.c_void_p), ("nnc_start", ctypes.c_void_p), ("nnc_rec", ctypes.c_void_p)]
+                ("nnc_geom", ctypes.c_void_p), ("nnc_start", ctypes.c_void_p), ("nnc_rec", ctypes.c_void_p),
+                ("nn_cells_wide", ctypes.c_int), ("pad_w", ctypes.c_int)]
 
 
 class WarpJob(ctypes.Structure):
@@ -86,6 +87,7 @@ MAX_WARP_JOBS = 32
 TICK_KERNELS = ("k_eng_fwd", "k_eng_nn", "k_eng_loss", "k_eng_bwd2", "k_eng_bwd1", "k_eng_update")   # one tick, launch order
 MAX_LOAD_JOBS = 16
 NNC_START = 4104                     # NDP_NNC_START: ints per cell_start table of the cell search
+NNC_MAX, NNW_MAX = 2048, 8192        # points per cloud of the cell search (nn_cells) and of its wide form (nn_cells_wide)
 
 
 def _closure(sources):
@@ -210,6 +212,9 @@ _SIGS = {
     "ndp_chamfer_nn_cells": [V, I, V, I, V, V, V, V, V, V, V, V],
     "ndp_chamfer_nn_cells_workspace": [I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_engine_nn_cells_fits": [I, I],
+    "ndp_chamfer_nn_cells_wide": [V, I, V, I, V, V, V, V, V, V, V, V],
+    "ndp_chamfer_nn_cells_wide_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_engine_nn_cells_wide_fits": [I, I],
     "ndp_chamfer_l1_bwd": [V, I, V, I, F, V, V, V, V, V, V, I, V],
     "ndp_flow_metrics": [V, V, V, I, V, V],
     "ndp_landmark_mse_fwd_bwd": [V, V, I, V, V, V],

@@ -180,6 +180,10 @@ static int check_engine(const ndp_engine *e, const char *who) {
         snprintf(g_err, sizeof g_err, "%s: null buffer", who);
         return NDP_E_INVALID;
     }
+    if (e->nn_cells && e->nn_cells_wide) {
+        snprintf(g_err, sizeof g_err, "%s: nn_cells and nn_cells_wide together (one search takes the nearest-neighbour stage)", who);
+        return NDP_E_INVALID;
+    }
     if ((e->gemm_mode & 6) && !e->gmax) {
         snprintf(g_err, sizeof g_err, "%s: the split backward (gemm_mode & 6) needs the gmax buffer", who);
         return NDP_E_INVALID;
@@ -198,6 +202,18 @@ static int check_nn_cells(const ndp_engine *e, const char *who) {
     }
     if (int rc = set_smem((const void *)k_eng_nn_cells_build, NNC_LDS_BYTES)) return rc;
     return set_smem((const void *)k_eng_nn_cells, NNC_LDS_BYTES);
+}
+
+static int check_nn_cells_wide(const ndp_engine *e, const char *who) {
+    if (!nnw_fits(e->n_cap, e->t_cap)) {
+        snprintf(g_err, sizeof g_err, "%s: nn_cells_wide needs n_cap and t_cap <= %d (ndp_engine_nn_cells_wide_fits)", who, NNW_MAX);
+        return NDP_E_UNSUPPORTED;
+    }
+    if (!e->nnc_geom || !e->nnc_start || !e->nnc_rec || !aligned16(e->nnc_start) || !aligned16(e->nnc_rec)) {
+        snprintf(g_err, sizeof g_err, "%s: nn_cells_wide without its grid buffers (nnc_geom [B][8], nnc_start [B][2][NDP_NNC_START], nnc_rec [B][t_cap + n_cap][4]; 16-byte aligned)", who);
+        return NDP_E_INVALID;
+    }
+    return set_smem((const void *)k_eng_nn_cells_wide, NNW_LDS_BYTES);
 }
 
 extern "C" int ndp_engine_load(const ndp_engine *e, int tick, const ndp_load_job *jobs, int n_jobs, void *stream) {
@@ -236,6 +252,11 @@ extern "C" int ndp_engine_load(const ndp_engine *e, int tick, const ndp_load_job
         if (int rc = check_nn_cells(e, "ndp_engine_load")) return rc;
         hipLaunchKernelGGL(k_eng_nn_cells_build, dim3(n_jobs), dim3(NNC_NT), NNC_LDS_BYTES, (hipStream_t)stream, *e, lj);
         HIP_TRY(hipGetLastError(), "k_eng_nn_cells_build launch");
+    }
+    if (e->nn_cells_wide && e->w_cd != 0.f && e->t_cap > 0) {
+        if (int rc = check_nn_cells_wide(e, "ndp_engine_load")) return rc;
+        hipLaunchKernelGGL(k_eng_nnw_build, dim3(n_jobs), dim3(NNW_NT), NNW_SORT_LDS_BYTES, (hipStream_t)stream, *e, lj);
+        HIP_TRY(hipGetLastError(), "k_eng_nnw_build launch");
     }
     return 0;
 }
@@ -306,6 +327,9 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
     }
     const bool nn_cells = nn && e->nn_cells != 0;                  // the cell search takes the NN stage's slot, whatever nn_mode names
     if (nn_cells) if (int rc = check_nn_cells(e, "ndp_engine_run")) return rc;
+    const bool nn_wide = nn && e->nn_cells_wide != 0;              // ... and so does the search for up to 8192 points
+    if (nn_wide) if (int rc = check_nn_cells_wide(e, "ndp_engine_run")) return rc;
+    const int nnw_q = nnw_chunks(e->n_cap, e->t_cap);
     // the matrix-pipe kernel in its 8-wave shape (512 targets per workgroup) where its LDS table fits
     const bool nn_mx8 = eng_nn_mx8(*e);
     const dim3 blk(256);
@@ -346,6 +370,10 @@ static int engine_launch_ticks(const ndp_engine *e, int tick0, int n_ticks, hipS
         NDP_EV();
         if (!NDP_ST(1)) {}
         else if (nn_cells) hipLaunchKernelGGL(k_eng_nn_cells, dim3(2, e->B), dim3(NNC_NT), NNC_LDS_BYTES, s, *e, parity);
+        else if (nn_wide) {
+            hipLaunchKernelGGL(k_eng_nnw_sort, dim3(e->B), dim3(NNW_NT), NNW_SORT_LDS_BYTES, s, *e, parity);
+            hipLaunchKernelGGL(k_eng_nn_cells_wide, dim3(2 * nnw_q, e->B), dim3(NNW_NT), NNW_LDS_BYTES, s, *e, parity, nnw_q);
+        }
         else if (nn && e->nn_mode == 1 && e->B <= 2) hipLaunchKernelGGL(k_eng_nn_lat16, g_nn_lat, dim3(1024), (3 * NN_STAGE + 2 * 1024) * 4, s, *e, parity);
         else if (nn && e->nn_mode == 1) hipLaunchKernelGGL(k_eng_nn_lat8, g_nn_lat, dim3(512), (3 * NN_STAGE + 2 * 512) * 4, s, *e, parity);
         else if (nn_mx8) hipLaunchKernelGGL(k_eng_nn_mx8, dim3((e->t_cap + 511) / 512, e->B), dim3(512), nn2_lds_floats(e->n_cap, 8) * 4, s, *e, parity);
@@ -431,6 +459,27 @@ extern "C" int ndp_chamfer_nn_cells(const float *x, int S, const float *y, int T
     hipLaunchKernelGGL(k_nn_cells_build, dim3(1), dim3(NNC_NT), NNC_LDS_BYTES, s, y, T, workspace);
     hipLaunchKernelGGL(k_nn_cells, dim3(2), dim3(NNC_NT), NNC_LDS_BYTES, s, x, S, y, T, prev_idx_x, prev_idx_y, d2x, idx_x, d2y, idx_y, workspace);
     HIP_TRY(hipGetLastError(), "k_nn_cells launch");
+    return 0;
+}
+extern "C" int ndp_engine_nn_cells_wide_fits(int n_cap, int t_cap) { return nnw_fits(n_cap, t_cap) ? 1 : 0; }
+extern "C" int ndp_chamfer_nn_cells_wide_workspace(int S, int T, long long *floats) {
+    if (S < 0 || T < 0 || !floats) return fail(NDP_E_INVALID, "ndp_chamfer_nn_cells_wide_workspace: bad arguments");
+    *floats = nnw_ws_floats(S, T);
+    return 0;
+}
+extern "C" int ndp_chamfer_nn_cells_wide(const float *x, int S, const float *y, int T, const int *prev_idx_x, const int *prev_idx_y,
+                                         float *d2x, int *idx_x, float *d2y, int *idx_y, float *workspace, void *stream) {
+    if (S <= 0 || T <= 0 || !x || !y || !d2x || !idx_x || !d2y || !idx_y || !workspace || !aligned16(workspace))
+        return fail(NDP_E_INVALID, "ndp_chamfer_nn_cells_wide: bad arguments (the workspace must be 16-byte aligned)");
+    if (!nnw_fits(S, T)) return fail(NDP_E_UNSUPPORTED, "ndp_chamfer_nn_cells_wide: S and T must be <= 8192 (ndp_engine_nn_cells_wide_fits)");
+    if (int rc = set_smem((const void *)k_nn_cells_wide, NNW_LDS_BYTES)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int Q = nnw_chunks(S, T);
+    hipLaunchKernelGGL(k_nnw_build, dim3(1), dim3(NNW_NT), NNW_SORT_LDS_BYTES, s, y, T, workspace);
+    hipLaunchKernelGGL(k_nnw_sort, dim3(1), dim3(NNW_NT), NNW_SORT_LDS_BYTES, s, x, S, T, workspace);
+    hipLaunchKernelGGL(k_nn_cells_wide, dim3(2 * Q), dim3(NNW_NT), NNW_LDS_BYTES, s, x, S, y, T, prev_idx_x, prev_idx_y, d2x, idx_x, d2y, idx_y,
+                       workspace, Q);
+    HIP_TRY(hipGetLastError(), "k_nn_cells_wide launch");
     return 0;
 }
 extern "C" int ndp_engine_nn_onepass_fits(int n_cap) { return nn1_lds_floats(n_cap, nn1_stage_x(n_cap)) * 4 <= 160 * 1024 ? 1 : 0; }

@@ -88,7 +88,7 @@ __device__ __forceinline__ void eng_loss_body(const ndp_engine &e, int parity, i
     const int *idx_y = e.idx_y + (size_t)b * e.t_cap;
     // nearest target of a source: folded here from the one-pass kernel's per-chunk partials (nn_row_fold)
     const NnPart *rowpart = reinterpret_cast<const NnPart *>(e.nn_row) + (size_t)b * nn1_row_chunks(e.t_cap) * e.n_cap;
-    const bool rows_final = e.nn_mode == 1 || e.nn_cells != 0;       // latency shape / cell search: d2x / idx_x already hold the answer
+    const bool rows_final = e.nn_mode == 1 || e.nn_cells != 0 || e.nn_cells_wide != 0;       // latency shape / cell search: d2x / idx_x already hold the answer
     const int rows_cstep = eng_nn_mx8(e) ? 2 : 1;    // the 8-wave matrix-pipe kernel leaves one partial per 512 targets
     const bool use_cd = gm.S > 0 && e.w_cd != 0.f;
     const HeadCfg hcl = make_head_cfg(desc_at_level(e.desc, st.level));

@@ -29,6 +29,7 @@
 #include "ndp_nsfp.inc"                // NSFP baseline: kernels, ndp_nsfp_fwd / _bwd
 #include "ndp_eng_load.inc"            // pair preparation and slot (re)fill: k_pair_means*, LoadJobs, k_eng_load
 #include "ndp_nn_cells.inc"            // exact grid ball search (behind LoadJobs: its grid-build kernel rides behind k_eng_load)
+#include "ndp_nn_cells_wide.inc"       // the same search for clouds of up to 8192 points: grids sorted in global memory, queries split over workgroups
 #include "ndp_abi.inc"                 // host entries that choose between the files above: level / pyramid / engine load, tick, NN shapes, operators
 #include "ndp_flow_metrics.inc"        // scene-flow metrics: k_flow_metrics, ndp_flow_metrics
 #include "ndp_nerfies.inc"             // Nerfies baseline

@@ -42,7 +42,7 @@
 //   by the NUMBER of record reads and evaluations a wave issues -- as many as its busiest lane needs -- not by their latency: reading
 //   2 / 4 / 8 records of a cell row together (the surplus re-reads the last one) measured 0.065 / 0.073 / 0.102 ms and was not kept; nor
 //   were queries taken in cell order (0.060) or a first look into the query's own cell to tighten a stale seed's bound (0.062).
-//   LDS per workgroup: records 32 KB + cell_start 16 KB.  Scope: S, T <= NNC_MAX (configs A and B); larger engines keep the dense kernels.
+//   LDS per workgroup: records 32 KB + cell_start 16 KB.  Scope: S, T <= NNC_MAX (configs A and B); up to 8192: ndp_nn_cells_wide.inc.
 // ------------------------------------------------------------------------------------------------
 #define NNC_NG 16
 #define NNC_NC (NNC_NG * NNC_NG * NNC_NG)

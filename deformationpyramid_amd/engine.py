@@ -50,6 +50,11 @@ DEFAULT_NN_MATRIX = True
 #   nn cells  : the NN stage as an exact grid ball search seeded by last tick's neighbours (bit-identical results) wherever the engine
 #               itself chose a one-pass shape and n_cap, t_cap <= 2048; nn_mode still names the dense kernel it replaces.
 DEFAULT_NN_CELLS = True
+#   nn cells wide: the same search for clouds of up to 8192 points (csrc/ndp_nn_cells_wide.inc, bit-identical results) where nn cells does
+#               not fit: the engine itself chose a one-pass shape, nn_cells resolved false, n_cap and t_cap <= 8192.  On because both
+#               workloads it was built for are faster than the dense kernel beyond their spread, same bits (bench.py --config C: 345 ->
+#               500 / 533 pairs/s, --config D: 395 -> 555 / 582; profiles/nn_cells_wide_bench_ab.txt).
+DEFAULT_NN_CELLS_WIDE = True
 # every bit gemm_mode may carry (ndp_hip.h); bits 64, 128, 256 and 512 selected measured variants until ABI 204 and are refused
 GEMM_MODE_BITS = 1 | 2 | 4 | 8 | 16 | 32 | 1024
 
@@ -101,6 +106,23 @@ def resolve_nn_cells(n_cap, t_cap, nn_mode_given, nn_mode, nn_cells=None):
     return bool(nn_cells)
 
 
+def resolve_nn_cells_wide(n_cap, t_cap, nn_mode_given, nn_mode, nn_cells, nn_cells_wide=None):
+    """-> whether the engine's nearest-neighbour stage is the grid ball search for up to 8192 points (csrc/ndp_nn_cells_wide.inc).
+    nn_cells: what resolve_nn_cells gave.  None: on where DEFAULT_NN_CELLS_WIDE is, the engine itself chose a one-pass shape (no nn_mode
+    given, nn_mode 0 or 2), nn_cells resolved false and the capacities fit (ndp_engine_nn_cells_wide_fits: both <= 8192).  True with
+    capacities that do not fit, or together with nn_cells, raises; True with an explicit nn_mode is allowed, as it is for nn_cells."""
+    fits = bool(N.lib().ndp_engine_nn_cells_wide_fits(n_cap, t_cap))
+    if nn_cells_wide is None:
+        return bool(DEFAULT_NN_CELLS_WIDE and nn_mode_given is None and nn_mode != 1 and not nn_cells and fits)
+    if nn_cells_wide and not fits:
+        raise N.NdpError(f"nn_cells_wide: n_cap = {n_cap}, t_cap = {t_cap} do not fit the wide cell search (ndp_engine_nn_cells_wide_fits: "
+                         "both <= 8192); leave nn_cells_wide unset and the engine keeps its dense kernel")
+    if nn_cells_wide and nn_cells:
+        raise N.NdpError("nn_cells_wide together with nn_cells: one search takes the nearest-neighbour stage; at n_cap, t_cap <= 2048 leave "
+                         "nn_cells_wide unset (or pass nn_cells=False)")
+    return bool(nn_cells_wide)
+
+
 class Snapshot:
     """Host copy of the [B] pair states of one tick."""
     __slots__ = ("raw", "sz", "level")
@@ -117,7 +139,7 @@ class Snapshot:
 
 
 class BatchedEngine:
-    def __init__(self, desc: LayerDesc, cfg: OptConfig, B: int, n_cap: int, t_cap: int, device, G=None, nn_mode=None, gemm_mode=None, nn_matrix=None, nn_cells=None):
+    def __init__(self, desc: LayerDesc, cfg: OptConfig, B: int, n_cap: int, t_cap: int, device, G=None, nn_mode=None, gemm_mode=None, nn_matrix=None, nn_cells=None, nn_cells_wide=None):
         # desc.nonrigidity = True means "every level but the first carries the gate" (nets.py:26); P is then the
         # parameter count of a gated level and level 0 uses a prefix-compatible shorter layout.
         self.lib = N.lib()
@@ -126,6 +148,7 @@ class BatchedEngine:
         # modes are resolved and validated HERE, once (see resolve_modes): nothing later reads the environment
         self.gemm_mode, self.nn_mode = resolve_modes(B, self.n_cap, self.t_cap, gemm_mode, nn_mode, nn_matrix)
         self.nn_cells = resolve_nn_cells(self.n_cap, self.t_cap, nn_mode, self.nn_mode, nn_cells)
+        self.nn_cells_wide = resolve_nn_cells_wide(self.n_cap, self.t_cap, nn_mode, self.nn_mode, self.nn_cells, nn_cells_wide)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise N.NdpError("BatchedEngine needs a GPU device; there is no CPU fallback")
@@ -162,6 +185,10 @@ class BatchedEngine:
             self.nnc_geom = torch.zeros(B, 8, **f32)
             self.nnc_start = torch.zeros(B, N.NNC_START, device=d, dtype=torch.int32)
             self.nnc_rec = torch.zeros(B, self.t_cap, 4, **f32)
+        if self.nn_cells_wide:           # the wide search keeps both grids in the same three buffers: [targets' | warped sources'] (ndp_hip.h)
+            self.nnc_geom = torch.zeros(B, 8, **f32)
+            self.nnc_start = torch.zeros(B, 2, N.NNC_START, device=d, dtype=torch.int32)
+            self.nnc_rec = torch.zeros(B, self.t_cap + self.n_cap, 4, **f32)
         tab = np.zeros((cfg.iters + 1, 2), dtype=np.float32)
         for t in range(1, cfg.iters + 1):
             tab[t] = adam_scalars(t, cfg.lr)
@@ -193,7 +220,8 @@ class BatchedEngine:
                      "d2x", "idx_x", "d2y", "idx_y", "adam_tab", "dO", "nn_row", "gmax"):
             setattr(e, name, getattr(self, name).data_ptr())
         e.nn_cells = int(self.nn_cells)
-        if self.nn_cells:
+        e.nn_cells_wide = int(self.nn_cells_wide)
+        if self.nn_cells or self.nn_cells_wide:
             for name in ("nnc_geom", "nnc_start", "nnc_rec"):
                 setattr(e, name, getattr(self, name).data_ptr())
         self.c_engine = e

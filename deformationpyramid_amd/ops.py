@@ -232,6 +232,24 @@ def chamfer_nn_cells(x, y, prev_idx_x=None, prev_idx_y=None):
     return d2x, ix, d2y, iy
 
 
+def chamfer_nn_cells_wide(x, y, prev_idx_x=None, prev_idx_y=None):
+    """chamfer_nn_cells for clouds of up to 8192 points (the NN stage of an engine with nn_cells_wide, as an operator): same result as
+    chamfer_nn for ANY prev_idx_x [S] / prev_idx_y [T] (int32, optional)."""
+    _chk(x, "x"); _chk(y, "y")
+    S, T = x.shape[0], y.shape[0]
+    for p, n, name in ((prev_idx_x, S, "prev_idx_x"), (prev_idx_y, T, "prev_idx_y")):
+        if p is not None and (p.dtype != torch.int32 or not p.is_cuda or not p.is_contiguous() or p.numel() != n):
+            raise ValueError(f"{name} must be a contiguous int32 device tensor with one entry per query")
+    nf = ctypes.c_longlong()
+    N.check(N.lib().ndp_chamfer_nn_cells_wide_workspace(S, T, ctypes.byref(nf)), "ndp_chamfer_nn_cells_wide_workspace")
+    ws = torch.empty(nf.value, device=x.device)
+    d2x = torch.empty(S, device=x.device); d2y = torch.empty(T, device=x.device)
+    ix = torch.empty(S, device=x.device, dtype=torch.int32); iy = torch.empty(T, device=x.device, dtype=torch.int32)
+    N.check(N.lib().ndp_chamfer_nn_cells_wide(_p(x), S, _p(y), T, _p(prev_idx_x), _p(prev_idx_y), _p(d2x), _p(ix), _p(d2y), _p(iy), _p(ws),
+                                              N.stream_ptr(x.device)), "ndp_chamfer_nn_cells_wide")
+    return d2x, ix, d2y, iy
+
+
 def chamfer_l1(x, y, trunc, nn=None, want_grad=True, point_sum=False, want_grad_y=False):
     """-> (loss [1], gx [S,3] | None, nn tuple).  point_sum: point_reduction="sum" of loss.py:233-235.
     want_grad_y: -> (loss, gx, nn, gy [T,3]).  The loss is symmetric in its clouds, so gy is the same kernel with the two clouds and

@@ -37,13 +37,14 @@ from .nets import _draw_ops, _native_rng_ok, init_pyramid_store
 
 
 class Registration:
-    def __init__(self, config, gemm_mode=None, nn_mode=None, nn_matrix=None, nn_cells=None):
+    def __init__(self, config, gemm_mode=None, nn_mode=None, nn_matrix=None, nn_cells=None, nn_cells_wide=None):
         """config: the reference's attribute-accessible config (NDP.yaml / LNDP.yaml keys).  gemm_mode / nn_mode (extension, both
         default to the engine's choice, see engine.resolve_modes): arithmetic of the level kernels' 128x128 contractions (0: fp32
         MFMA, bitwise the oracle's chain; 7: two-way fp16 splits on the fp16 MFMA), a forced shape of the nearest-neighbour kernel
         (nn_mode) or just the preference for its matrix-pipe variant where the engine picks the throughput shape (nn_matrix).
-        nn_cells: the nearest-neighbour stage as the exact grid ball search (None: the engine's choice, engine.resolve_nn_cells)."""
-        self.gemm_mode, self.nn_mode, self.nn_matrix, self.nn_cells = gemm_mode, nn_mode, nn_matrix, nn_cells
+        nn_cells: the nearest-neighbour stage as the exact grid ball search (None: the engine's choice, engine.resolve_nn_cells).
+        nn_cells_wide: the same search for clouds of up to 8192 points (None: the engine's choice, engine.resolve_nn_cells_wide)."""
+        self.gemm_mode, self.nn_mode, self.nn_matrix, self.nn_cells, self.nn_cells_wide = gemm_mode, nn_mode, nn_matrix, nn_cells, nn_cells_wide
         self.tgt_pcd = None
         self.src_pcd = None
         self.landmarks = None
@@ -391,12 +392,12 @@ class Registration:
         t_cap = ops.cap(max(like.T, self.config.samples if like.S else 0))
         cfg = self._opt_config(like.K > 0)
         desc = like.desc
-        key = (B, n_cap, t_cap, desc, tuple(sorted(vars(cfg).items())), self.gemm_mode, self.nn_mode, self.nn_matrix, self.nn_cells)
+        key = (B, n_cap, t_cap, desc, tuple(sorted(vars(cfg).items())), self.gemm_mode, self.nn_mode, self.nn_matrix, self.nn_cells, self.nn_cells_wide)
         if self._engines.get("key") != key:
             self._engines.clear()                      # one resident engine configuration at a time
             self._engines["key"] = key
         if lane not in self._engines:
-            self._engines[lane] = BatchedEngine(desc, cfg, B, n_cap, t_cap, self._dev(), gemm_mode=self.gemm_mode, nn_mode=self.nn_mode, nn_matrix=self.nn_matrix, nn_cells=self.nn_cells)
+            self._engines[lane] = BatchedEngine(desc, cfg, B, n_cap, t_cap, self._dev(), gemm_mode=self.gemm_mode, nn_mode=self.nn_mode, nn_matrix=self.nn_matrix, nn_cells=self.nn_cells, nn_cells_wide=self.nn_cells_wide)
         return self._engines[lane]
 
     def _finish(self, eng, done, freeze=False, frozen=None):

@@ -226,6 +226,17 @@ int ndp_chamfer_nn_cells_workspace(int T, long long *floats);
 /* 1 when an engine of these capacities can search by cells (ndp_engine.nn_cells): both <= 2048. */
 int ndp_engine_nn_cells_fits(int n_cap, int t_cap);
 
+/* The grid ball search for clouds of up to 8192 points (what an engine with nn_cells_wide runs every tick; csrc/ndp_nn_cells_wide.inc): the
+ * same algorithm, geometry and result -- bit-identical to ndp_chamfer_nn_fwd for ANY seeds -- with both grids sorted in global memory (the
+ * sources' by a launch of its own) and the queries of a direction split over workgroups of 2048.  Arguments as for ndp_chamfer_nn_cells;
+ * workspace: ndp_chamfer_nn_cells_wide_workspace(S, T) floats, 16-byte aligned.
+ * 1 <= S, T <= 8192 (ndp_engine_nn_cells_wide_fits); beyond that NDP_E_UNSUPPORTED.                                                    */
+int ndp_chamfer_nn_cells_wide(const float *x, int S, const float *y, int T, const int *prev_idx_x, const int *prev_idx_y,
+                              float *d2x, int *idx_x, float *d2y, int *idx_y, float *workspace, void *stream);
+int ndp_chamfer_nn_cells_wide_workspace(int S, int T, long long *floats);
+/* 1 when an engine of these capacities can run the wide cell search (ndp_engine.nn_cells_wide): both in 1..8192. */
+int ndp_engine_nn_cells_wide_fits(int n_cap, int t_cap);
+
 /* Truncated L1 Chamfer value and gradient from the NN result (loss.py:185-258 and its autograd):
  * loss[0] = sum_i sqrt(d2x_i)[d2x_i<trunc]/S + sum_j sqrt(d2y_j)[d2y_j<trunc]/T   (point_sum != 0: without the /S, /T --
  * point_reduction="sum", loss.py:233-235) ;
@@ -344,6 +355,13 @@ typedef struct ndp_engine {
     float *nnc_geom;                 /* [B][8] grid geometry per pair: origin[3], cells per unit length[3], 2 pad (NULL without nn_cells) */
     int *nnc_start;                  /* [B][NDP_NNC_START] cell_start of the targets' grid, x fastest (NULL without nn_cells)            */
     float *nnc_rec;                  /* [B][t_cap][4] the targets sorted by cell: {x, y, z, index bits}, 16-byte aligned (NULL without)   */
+    int nn_cells_wide, pad_w;        /* ABI 208.  nn_cells_wide != 0: the nearest-neighbour stage is the grid ball search for up to 8192
+                                        points per cloud (csrc/ndp_nn_cells_wide.inc: k_eng_nnw_sort + k_eng_nn_cells_wide, bit-identical
+                                        results, needs ndp_engine_nn_cells_wide_fits(n_cap, t_cap)) in place of the dense kernel nn_mode
+                                        names.  Not together with nn_cells.  The grids live in the three buffers above in a layout of their
+                                        own: nnc_geom [B][8] as there; nnc_start [B][2][NDP_NNC_START]: the targets' cell_start table, then
+                                        the warped sources' (rewritten every tick); nnc_rec [B][t_cap + n_cap][4]: the targets' records,
+                                        then the warped sources'.  ndp_engine_load builds the grid of a slot's targets.                    */
 } ndp_engine;
 #define NDP_NNC_START 4104           /* ints per cell_start table: 16^3 + 1 entries, padded to a multiple of 4 */
 

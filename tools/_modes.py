@@ -1,4 +1,4 @@
-"""Engine modes for the measurement tools: NDP_GEMM_MODE / NDP_NN_MODE / NDP_NN_CELLS (0 / 1) in the environment -> Registration / BatchedEngine
+"""Engine modes for the measurement tools: NDP_GEMM_MODE / NDP_NN_MODE / NDP_NN_CELLS / NDP_NN_CELLS_WIDE (0 / 1) in the environment -> Registration / BatchedEngine
 keyword arguments.  (The package itself reads no environment variable: modes are constructor arguments.)"""
 import os
 
@@ -18,4 +18,6 @@ def from_env():
         kw["nn_mode"] = nn
     if os.environ.get("NDP_NN_CELLS"):
         kw["nn_cells"] = bool(int(os.environ["NDP_NN_CELLS"]))
+    if os.environ.get("NDP_NN_CELLS_WIDE"):
+        kw["nn_cells_wide"] = bool(int(os.environ["NDP_NN_CELLS_WIDE"]))
     return kw

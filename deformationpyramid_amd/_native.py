@@ -32,6 +32,16 @@ class NdpError(RuntimeError):
     pass
 
 
+class NdpUnservedError(NdpError, KeyError):
+    """Registration.register() was asked for something this package does not serve: a `deformation_model` it has no path for, or
+    any model on a CPU device (there is no CPU fallback).  One class for both, and both of its bases on purpose: callers that treat
+    "not served here" as a failed lookup of the model (`except KeyError`, what an unknown model has always raised) and callers that
+    catch the package's own NdpError keep working whichever of the two reasons applies."""
+
+    def __str__(self):
+        return RuntimeError.__str__(self)              # the message itself, not KeyError's repr of it
+
+
 class PairGeom(ctypes.Structure):
     _fields_ = [("K", ctypes.c_int), ("S", ctypes.c_int), ("T", ctypes.c_int), ("pad", ctypes.c_int)]
 
@@ -223,6 +233,9 @@ _SIGS = {
     "ndp_engine_run_timed": [ctypes.POINTER(Engine), I, I, V, c_float_p],
     "ndp_engine_run_stages": [ctypes.POINTER(Engine), I, I, I, V],
     "ndp_engine_load": [ctypes.POINTER(Engine), I, ctypes.POINTER(LoadJob), I, V],
+    "ndp_sinkhorn_schedule": [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double), I],
+    "ndp_sinkhorn_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_sinkhorn_divergence": [V, I, V, I, F, F, F, ctypes.c_double, V, V, V, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

@@ -35,3 +35,4 @@
 #include "ndp_nerfies.inc"             // Nerfies baseline
 #include "ndp_ed.inc"                  // embedded-deformation N-ICP baseline
 #include "ndp_jacobian.inc"            // warp with its per-point Jacobian, inverse warp
+#include "ndp_sinkhorn.inc"            // Sinkhorn divergence baseline: streamed soft-minimum step / final kernels, fixed-order loss reduce

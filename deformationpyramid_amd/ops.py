@@ -270,6 +270,31 @@ def chamfer_l1(x, y, trunc, nn=None, want_grad=True, point_sum=False, want_grad_
     return loss, gx, nn, gy
 
 
+def sinkhorn_divergence(x, y, blur, reach=None, scaling=0.5, want_grad=True, want_potentials=False):
+    """Debiased Sinkhorn divergence of two uniformly weighted clouds x [n,3], y [m,3], cost |u - v|^2 / 2 (the arithmetic of
+    geomloss.SamplesLoss("sinkhorn", p=2, blur, reach, scaling) as restated in DESIGN.md; reach None: balanced).
+    -> (loss [1], grad_x [n,3] | None, potentials [2n + 2m] = (F_ba, F_aa, G_ab, G_bb) | None).  grad_x is dloss/dx with y and the
+    dual potentials held fixed.  One host read: the diameter of the joint bounding box, as the library's `.item()`."""
+    _chk(x, "x"); _chk(y, "y")
+    for t, name in ((x, "x"), (y, "y")):
+        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"{name} must be a [N, 3] tensor with N >= 1, got {tuple(t.shape)}")
+    n, m = x.shape[0], y.shape[0]
+    lo = torch.minimum(x.min(dim=0).values, y.min(dim=0).values).double()
+    hi = torch.maximum(x.max(dim=0).values, y.max(dim=0).values).double()
+    diameter = float((hi - lo).norm().item())
+    nf = ctypes.c_longlong()
+    N.check(N.lib().ndp_sinkhorn_workspace(n, m, ctypes.byref(nf)), "ndp_sinkhorn_workspace")
+    ws = torch.empty(nf.value // 2 + 1, device=x.device, dtype=torch.float64)       # (float64: 8-byte aligned)
+    loss = torch.empty(1, device=x.device)
+    gx = torch.empty_like(x) if want_grad else None
+    pot = torch.empty(2 * n + 2 * m, device=x.device) if want_potentials else None
+    N.check(N.lib().ndp_sinkhorn_divergence(_p(x), n, _p(y), m, float(blur), 0.0 if reach is None else float(reach), float(scaling),
+                                            diameter, _p(ws), _p(loss), _p(gx), _p(pot), N.stream_ptr(x.device)),
+            "ndp_sinkhorn_divergence")
+    return loss, gx, pot
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)

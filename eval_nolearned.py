@@ -16,8 +16,8 @@ then `compute_flow_metrics` averaged by `AverageMeter`, then the timer report.  
 * under `torchrun` (WORLD_SIZE > 1) the pairs of each benchmark are sharded over the ranks, one GPU per rank
   (`parallel.shard_range`), and the per-metric sums are combined by ONE all-reduce (RCCL; `NDP_BENCH_BACKEND=gloo` for a
   rehearsal on a box with one GPU) -- BASELINE.json config 3, "4DMatch-F full split batched across 8 GPUs";
-* `deformation_model: NDP` and the `NSFP` / `Nerfies` baselines (config/baselines/*.yaml) are served; the other models
-  are comparison baselines outside the scope.
+* `deformation_model: NDP` and the `NSFP` / `Nerfies` / `NICP` (`ED`) / `Sinkhorn` baselines (config/baselines/*.yaml) are
+  served; `Lepard+NICP` needs a learned matcher and is outside the scope.
 """
 import argparse
 import glob
@@ -150,7 +150,7 @@ def main():
     world, rank, local_rank, backend = dist_setup()
     setup_seed(rank)                                                        # once per process, as upstream (seed 0 on one GPU)
     config = load_config(args.config, make_dirs=rank == 0, device=local_rank)
-    if config.deformation_model not in ("NDP", "NSFP", "Nerfies", "ED"):
+    if config.deformation_model not in ("NDP", "NSFP", "Nerfies", "ED", "Sinkhorn"):
         raise KeyError(config.deformation_model)
     model = Registration(config)
     timer = Timers()
@@ -195,6 +195,18 @@ def main():
                 torch.cuda.synchronize()
                 timer.toc("registration")
                 flows.append((warped - model.src_pcd).cpu())
+        elif config.deformation_model == "Sinkhorn":                        # eval_nolearned.py:97-108: the moved samples only
+            flows, kept = [], []
+            for src, tgt, flow_gt, overlap in items:
+                model.load_pcds(src, tgt)
+                timer.tic("registration")
+                warped, smpl_ind = model.register(visualize=args.visualize)
+                torch.cuda.synchronize()
+                timer.toc("registration")
+                flows.append((warped - model.src_pcd[smpl_ind]).cpu())
+                ind = smpl_ind.cpu()
+                kept.append((src, tgt, flow_gt[ind], overlap[ind]))
+            items = kept
         elif args.batched:
             timer.tic("registration")
             results = model.register_batch([(s, t) for s, t, _, _ in items], slots=args.slots)

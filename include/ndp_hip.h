@@ -251,6 +251,27 @@ int ndp_chamfer_l1_bwd(const float *x, int S, const float *y, int T, float trunc
  * like upstream's mean over nothing).                                                                                 */
 int ndp_flow_metrics(const float *flow, const float *flow_gt, const unsigned char *overlap, int n, double *out15, void *stream);
 
+/* Sinkhorn divergence baseline (registration.py:543-572 calls geomloss.SamplesLoss("sinkhorn", p=2, blur, reach); csrc/ndp_sinkhorn.inc).
+ * The arithmetic is restated from the library's published algorithm (tensorized backend, debias, uniform weights, cost |u - v|^2 / 2)
+ * in DESIGN.md "Sinkhorn baseline"; parity with the library itself is unverified.
+ *
+ * ndp_sinkhorn_schedule (host only): eps_list = [diameter^2] + [exp(e) for e in arange(2 ln diameter, 2 ln blur, 2 ln scaling)] +
+ *   [blur^2] with numpy's arange (count ceil((stop - start) / step), none when diameter <= blur), in double.  Returns the number of
+ *   entries and writes the first min(count, cap) of them to eps_out (host memory; may be NULL when cap == 0).
+ * ndp_sinkhorn_workspace: *nfloats = 4 ceil(max(n, m) / 16) + 4 (n + m): one double per 16-row workgroup and side of the final
+ *   kernel (the loss partials), then the potentials [f_ba n | f_aa n | g_ab m | g_bb m] twice (every step reads one copy and writes
+ *   the other).  The workspace must be 8-byte aligned.
+ * ndp_sinkhorn_divergence: x [n][3], y [m][3]; reach <= 0: balanced; diameter: norm of the extent of the joint bounding box, read
+ *   by the caller.  loss_out: one device float; grad_x [n][3] (dloss/dx, the second cloud and the dual potentials held fixed) or
+ *   NULL; potentials [2n + 2m] = (F_ba [n], F_aa [n], G_ab [m], G_bb [m]) or NULL.  Any n, m >= 1: the columns are streamed, the
+ *   n x m matrix is never stored.  No atomics: the same inputs give the same bits.  1 + entries + 2 launches on `stream`.
+ *   NDP_E_INVALID: n < 1, m < 1, blur <= 0, scaling outside (0, 1), diameter not positive and finite, reach not finite, a NULL
+ *   x / y / ws / loss_out; NDP_E_UNSUPPORTED: a schedule of more than 256 entries.                                                */
+int ndp_sinkhorn_schedule(double diameter, double blur, double scaling, double *eps_out, int cap);
+int ndp_sinkhorn_workspace(int n, int m, long long *nfloats);
+int ndp_sinkhorn_divergence(const float *x, int n, const float *y, int m, float blur, float reach, float scaling, double diameter,
+                            float *ws, float *loss_out, float *grad_x, float *potentials, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

@@ -236,6 +236,9 @@ _SIGS = {
     "ndp_sinkhorn_schedule": [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double), I],
     "ndp_sinkhorn_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_sinkhorn_divergence": [V, I, V, I, F, F, F, ctypes.c_double, V, V, V, V, V],
+    "ndp_knn": [V, I, V, I, I, V, V, V],
+    "ndp_normals_from_knn": [V, I, V, I, V, V, V, V],
+    "ndp_point_to_plane": [V, I, V, I, V, V, F, V, V, V, V, I, V, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

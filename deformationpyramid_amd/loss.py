@@ -1,13 +1,14 @@
 """Loss and metric surface of the reference's model/loss.py, backed by the HIP Chamfer kernels.
 
     compute_truncated_chamfer_distance(x, y, ..., trunc=0.2)   (/root/reference/model/loss.py:94-258)
+    point_2_plane_distance(x, y, ..., x_normals, y_normals)    (loss.py:61-92)
     compute_flow_metrics(flow, flow_gt, overlap=None)          (loss.py:431-471)
     scene_flow_metrics(pred, labels, strict=0.025, relax=0.05) (loss.py:382-403)
     landmark_cost(x, y)                                        (loss.py:348-351)
 
 The nearest-neighbour search and the L1 reduction run in libndp_hip.so (no pytorch3d, no torch
-fallback for GPU tensors).  Normals / Pointclouds inputs are not part of any caller of the hot
-path and are rejected.
+fallback for GPU tensors).  Pointclouds inputs are not part of any caller of the hot path and are
+rejected; normals are taken by point_2_plane_distance only.
 """
 import torch
 
@@ -67,6 +68,28 @@ def compute_truncated_chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_n
     if batch_reduction == "mean":
         out = out / (weights.sum() if weights is not None else N)
     return out
+
+
+def point_2_plane_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, *, trunc=None, true_plane=False):
+    """model/loss.py:61-92 on the HIP kernels: x [1,P1,3], y [1,P2,3] with their normals -> (p2plane, x_2_plane, y_2_plane,
+    x_ref_normal [P1,3] = y_normals at every x point's nearest y point).  The defaults are the reference's arithmetic as written,
+    sqrt(sum_a ((x_a - p_a) n_a)^2): the norm of the elementwise product, which is not a plane distance; true_plane=True gives
+    |(x - p) . n|.  trunc (squared units, None: none) drops pairs as the Chamfer does.  p2plane is differentiable (first derivatives)
+    in x and in y with the normals and the nearest-neighbour indices held constant; x_2_plane and y_2_plane are its two parts as
+    values."""
+    if x_normals is None or y_normals is None:
+        raise ValueError("point_2_plane_distance needs x_normals and y_normals")
+    xl = _lengths(x, x_lengths, "x")
+    yl = _lengths(y, y_lengths, "y")
+    assert x.shape[0] == 1                                            # as the reference (loss.py:76)
+    if y.shape[0] != 1 or x.shape[2] != 3 or y.shape[2] != 3:
+        raise ValueError("expected x [1, P1, 3] and y [1, P2, 3]")
+    if x_normals.shape != x.shape or y_normals.shape != y.shape:
+        raise ValueError("normals must have the shapes of their clouds")
+    xb, yb = x[0, :xl[0]].float(), y[0, :yl[0]].float()
+    nxb, nyb = x_normals[0, :xl[0]].float().contiguous(), y_normals[0, :yl[0]].float().contiguous()
+    total, parts, idx_x = ops.point_to_plane_distance(xb, yb, nxb, nyb, float("inf") if trunc is None else trunc, 1 if true_plane else 0)
+    return total, parts[0], parts[1], y_normals[0][idx_x.long()]
 
 
 def landmark_cost(x, y):

@@ -295,6 +295,68 @@ def sinkhorn_divergence(x, y, blur, reach=None, scaling=0.5, want_grad=True, wan
     return loss, gx, pot
 
 
+def _cloud(t, name):
+    _chk(t, name)
+    if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{name} must be a [N, 3] tensor with N >= 1, got {tuple(t.shape)}")
+    return t
+
+
+def knn(q, r, K):
+    """The K nearest points of r [nr,3] for every point of q [nq,3], exact (csrc/ndp_normals.inc: k_knn)
+    -> (d2 [nq,K] squared distances, idx [nq,K] int32), every row ascending in (d2, index).  1 <= K <= 32, K <= nr; column 0 at
+    K = 1 is bitwise chamfer_nn's d2x / idx_x."""
+    _cloud(q, "q"); _cloud(r, "r")
+    nq, nr, K = q.shape[0], r.shape[0], int(K)
+    d2 = torch.empty(nq, max(K, 0), device=q.device)
+    idx = torch.empty(nq, max(K, 0), device=q.device, dtype=torch.int32)
+    N.check(N.lib().ndp_knn(_p(q), nq, _p(r), nr, K, _p(d2), _p(idx), N.stream_ptr(q.device)), "ndp_knn")
+    return d2, idx
+
+
+def normals_from_knn(p, idx, viewpoint=None, want_curvature=False):
+    """PCA normals of p [n,3] from neighbour lists idx [n,K] (int32, K >= 3, e.g. knn(p, p, K)[1]) -> normals [n,3], with
+    want_curvature (normals, curvature [n] = l0 / (l0 + l1 + l2)).  viewpoint (3 values): normals face it; None: the component of
+    largest magnitude is positive."""
+    _cloud(p, "p"); _chk(idx, "idx", torch.int32)
+    if idx.ndim != 2 or idx.shape[0] != p.shape[0]:
+        raise ValueError(f"idx must be [{p.shape[0]}, K], got {tuple(idx.shape)}")
+    vp = None
+    if viewpoint is not None:
+        vp = torch.as_tensor(viewpoint, dtype=torch.float32).reshape(3).to(p.device).contiguous()
+    normals = torch.empty_like(p)
+    curv = torch.empty(p.shape[0], device=p.device) if want_curvature else None
+    N.check(N.lib().ndp_normals_from_knn(_p(p), p.shape[0], _p(idx), idx.shape[1], _p(vp), _p(normals), _p(curv), N.stream_ptr(p.device)),
+            "ndp_normals_from_knn")
+    return (normals, curv) if want_curvature else normals
+
+
+def point_to_plane(x, y, nx, ny, trunc=math.inf, mode=0, nn=None, want_grad=True, want_grad_y=False):
+    """Point-to-plane residuals of both directions on one nearest-neighbour result -> (out [4], gx [S,3] | None, nn tuple), with
+    want_grad_y (out, gx, nn, gy [T,3]).  out = (sum, x part, y part, normal consistency); mode 0: the reference's formula
+    (model/loss.py:87-88, the norm of the elementwise product), mode 1: the plane distance |(x - p) . n|; trunc in squared units.
+    nn: chamfer_nn's tuple, so that a Chamfer term and a plane term share one search.  gy is the same entry with the clouds, the
+    normals and the halves of nn exchanged."""
+    _cloud(x, "x"); _cloud(y, "y"); _chk(nx, "nx"); _chk(ny, "ny")
+    if nx.shape != x.shape or ny.shape != y.shape:
+        raise ValueError("nx / ny must have the shapes of x / y")
+    if nn is None:
+        nn = chamfer_nn(x, y)
+    d2x, ix, d2y, iy = nn
+    S, T = x.shape[0], y.shape[0]
+    out = torch.empty(4, device=x.device)
+    gx = torch.empty_like(x) if want_grad else None
+    N.check(N.lib().ndp_point_to_plane(_p(x), S, _p(y), T, _p(nx), _p(ny), float(trunc), _p(d2x), _p(ix), _p(d2y), _p(iy), int(mode),
+                                       _p(out), _p(gx), N.stream_ptr(x.device)), "ndp_point_to_plane")
+    if not want_grad_y:
+        return out, gx, nn
+    gy = torch.empty_like(y)
+    out_y = torch.empty(4, device=x.device)                          # (the exchanged call's own copy of the values: not used)
+    N.check(N.lib().ndp_point_to_plane(_p(y), T, _p(x), S, _p(ny), _p(nx), float(trunc), _p(d2y), _p(iy), _p(d2x), _p(ix), int(mode),
+                                       _p(out_y), _p(gy), N.stream_ptr(x.device)), "ndp_point_to_plane")
+    return out, gx, nn, gy
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)
@@ -398,6 +460,33 @@ class _ChamferFn(torch.autograd.Function):
 def chamfer_distance(x, y, trunc, point_sum=False):
     """Differentiable (in x and in y, first derivatives) truncated L1 Chamfer of two [n,3] clouds."""
     return _ChamferFn.apply(x, y, float(trunc), bool(point_sum))
+
+
+class _PointToPlaneFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, nx, ny, trunc, mode):
+        xd, yd = x.detach().contiguous(), y.detach().contiguous()
+        res = point_to_plane(xd, yd, nx.detach().contiguous(), ny.detach().contiguous(), trunc, mode,
+                             want_grad=x.requires_grad, want_grad_y=y.requires_grad)
+        out, gx = res[0], res[1]
+        gy = res[3] if y.requires_grad else None
+        none = torch.empty(0, device=x.device)
+        ctx.save_for_backward(gx if gx is not None else none, gy if gy is not None else none)
+        parts = out[1:].clone()
+        ctx.mark_non_differentiable(parts, res[2][1])
+        return out[0], parts, res[2][1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, g_parts, g_idx):
+        gx, gy = ctx.saved_tensors
+        return (gx * g if gx.numel() else None), (gy * g if gy.numel() else None), None, None, None, None
+
+
+def point_to_plane_distance(x, y, nx, ny, trunc=math.inf, mode=0):
+    """-> (total, parts [3] = (x part, y part, normal consistency), idx_x [S] int32).  `total` is differentiable (first derivatives)
+    in x and in y; the normals and the nearest-neighbour indices are constants; `parts` are values only."""
+    return _PointToPlaneFn.apply(x, y, nx, ny, float(trunc), int(mode))
 
 
 def flow_metrics(flow, flow_gt, overlap=None):

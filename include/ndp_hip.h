@@ -272,6 +272,39 @@ int ndp_sinkhorn_workspace(int n, int m, long long *nfloats);
 int ndp_sinkhorn_divergence(const float *x, int n, const float *y, int m, float blur, float reach, float scaling, double diameter,
                             float *ws, float *loss_out, float *grad_x, float *potentials, void *stream);
 
+/* Surface normals (csrc/ndp_normals.inc; DESIGN.md "Surface normals").  Device pointers to contiguous fp32 / int32, nothing is
+ * allocated, no atomics: the same inputs give the same bits.  One launch each on `stream`.
+ *
+ * ndp_knn: the K nearest references of every query, exact, by brute force (pytorch3d knn_points with K > 1, one cloud pair).
+ *   q [nq][3], r [nr][3] -> d2 [nq][K] squared distances, idx [nq][K] reference indices, every row ascending in (d2, index): equal
+ *   distances are listed by lower index.  A distance is ndp_chamfer_nn_fwd's chain (d = q - r per axis, fmaf(dz, dz, fmaf(dy, dy,
+ *   dx * dx))), so column 0 at K = 1 is bit for bit its d2x / idx_x.  1 <= K <= 32, K <= nr, 1 <= nq, nr <= 16777216.
+ *   NDP_E_INVALID: K outside 1..32 or above nr, nq or nr < 1, a NULL pointer; NDP_E_UNSUPPORTED: more than 16777216 points.
+ * ndp_normals_from_knn: PCA normals.  p [n][3], idx [n][K] neighbour lists into p (K >= 3) -> normals [n][3], curvature [n] or NULL.
+ *   Per point, over its K listed neighbours: mean, covariance C = (1/K) sum (p_k - mean)(p_k - mean)^T from differences, in double;
+ *   normal = unit eigenvector of the smallest eigenvalue l0 (cyclic Jacobi in double, rounded to fp32 once); curvature =
+ *   l0 / (l0 + l1 + l2).  Sign: with viewpoint (3 device floats) n . (viewpoint - p_i) >= 0; with NULL the component of largest
+ *   magnitude is positive, the lowest axis winning ties.  A zero covariance gives the normal (0, 0, 0) and curvature 0; a row that
+ *   lists an index outside [0, n) is not read and gives NaN.
+ *   NDP_E_INVALID: K < 3, n < 1, a NULL p / idx / normals; NDP_E_UNSUPPORTED: more than 16777216 points.
+ * ndp_point_to_plane: both directions' point-to-plane residuals and their gradient from ONE nearest-neighbour result (the four
+ *   arrays of ndp_chamfer_nn_fwd).  Direction x: p = y[idx_x[i]], n = ny[idx_x[i]]; direction y: p = x[idx_y[j]], n = nx[idx_y[j]].
+ *   mode 0: r = sqrt(sum_a ((x_a - p_a) n_a)^2), the reference's arithmetic as written (loss.py:87-88: the norm of the elementwise
+ *   product, not a plane distance); mode 1: r = |sum_a (x_a - p_a) n_a|.
+ *   out[1] = (1/S) sum_i r_i [d2x_i < trunc], out[2] the same over y with 1/T (trunc in squared units, +inf: the reference),
+ *   out[0] = out[1] + out[2], out[3] = mean_i (1 - |cos(nx_i, ny[idx_x[i]])|) + mean_j (1 - |cos(ny_j, nx[idx_y[j]])|) (loss.py:200-210,
+ *   cosine_similarity with eps 1e-6: a zero normal gives cos = 0; not truncated).  gx [S][3] or NULL: d out[0] / dx, indices and
+ *   normals held constant, the terms direction y sends to x[idx_y[j]] added in ascending j.  mode 0 at r = 0 gives the reference's
+ *   NaN (sqrt's backward at 0); mode 1 uses sign(0) = 0.  The gradient in y is the same entry with the clouds, normals and
+ *   nearest-neighbour halves exchanged.
+ *   NDP_E_INVALID: mode other than 0 / 1, S or T < 1, a NULL pointer other than gx, trunc NaN.                                          */
+int ndp_knn(const float *q, int nq, const float *r, int nr, int K, float *d2, int *idx, void *stream);
+int ndp_normals_from_knn(const float *p, int n, const int *idx, int K, const float *viewpoint, float *normals, float *curvature,
+                         void *stream);
+int ndp_point_to_plane(const float *x, int S, const float *y, int T, const float *nx, const float *ny, float trunc,
+                       const float *d2x, const int *idx_x, const float *d2y, const int *idx_y, int mode, float *out, float *gx,
+                       void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

@@ -3,7 +3,7 @@
 euler deformation pyramid fitted between two meshes, then applied to every vertex of the source mesh.
 
     python shape_transfer.py -s sim3_demo/AlienSoldier.ply -t sim3_demo/Ortiz.ply [-o warped.ply]
-                             [--jacobian-stats] [--pull-back pulled.ply]
+                             [--jacobian-stats] [--pull-back pulled.ply] [--plane-stats]
 
 Same hard-wired settings as upstream (:27-52): 6000 surface samples per mesh, ALL of them used as Chamfer samples,
 m = 9, k0 = -8, lr 0.01, 500 iterations with the early-stop rule, Sim3 + euler; like upstream the target mean is
@@ -11,9 +11,11 @@ NOT added back to the warped vertices (:164-167).  The optimisation loop is the 
 level/Adam/early-stop semantics the upstream script spells out inline, :116-157); open3d mesh I/O and viewers are
 replaced by an ASCII-PLY reader/writer and an area-weighted sampler (deformationpyramid_amd/meshio.py).
 
-Two optional extras on top of upstream (without them the output is unchanged): --jacobian-stats prints det J of the fitted warp at
+Three optional extras on top of upstream (without them the output is unchanged): --jacobian-stats prints det J of the fitted warp at
 the mesh vertices (local volume change; det J <= 0 marks where the field folded over), --pull-back FILE maps the TARGET mesh's
-vertices into the source frame through the inverse warp (Registration.inverse_warp) and writes them with the target's faces.
+vertices into the source frame through the inverse warp (Registration.inverse_warp) and writes them with the target's faces,
+--plane-stats prints the mean point-to-plane residual |(x - p) . n| of the source samples against the target samples and their face
+normals before and after the fit (both clouds centred as the fit sees them): a quality figure that needs no ground truth.
 """
 import argparse
 
@@ -44,13 +46,15 @@ if __name__ == "__main__":
     ap.add_argument("--jacobian-stats", action="store_true", help="print min / median / max of det J at the warped vertices and the folded share")
     ap.add_argument("--pull-back", type=str, default="", metavar="FILE",
                     help="write the target mesh's vertices mapped into the source frame (inverse warp) here (ASCII PLY)")
+    ap.add_argument("--plane-stats", action="store_true",
+                    help="print the mean point-to-plane residual of the source samples against the target samples' normals before and after the fit")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
     src_v, src_f = read_ply_ascii(args.s)
     tgt_v, tgt_f = read_ply_ascii(args.t)
     src_pcd = sample_surface(src_v, src_f, config.samples, rng)
-    tgt_pcd = sample_surface(tgt_v, tgt_f, config.samples, rng)
+    tgt_pcd, tgt_nrm = sample_surface(tgt_v, tgt_f, config.samples, rng, return_normals=True)     # (the same draws and points as without)
 
     model = Registration(config)
     model.load_pcds(src_pcd, tgt_pcd)
@@ -72,6 +76,15 @@ if __name__ == "__main__":
         det = torch.linalg.det(J.double().cpu())
         print(f"det J at {det.numel()} vertices: min {det.min().item():.6g}  median {det.median().item():.6g}  max {det.max().item():.6g}"
               f"  folded (det J <= 0): {100.0 * (det <= 0).double().mean().item():.3f} %")
+    if args.plane_stats:
+        src_c = (torch.from_numpy(src_pcd).to(dev) - src_mean).contiguous()
+        tgt_c = torch.from_numpy(tgt_pcd).to(dev)
+        tgt_c = (tgt_c - tgt_c.mean(dim=0, keepdim=True)).contiguous()
+        ny = torch.from_numpy(tgt_nrm).to(dev).contiguous()
+        moved = ops.pyramid_fwd(eng.desc, config.m, config.k0, eng.params[0], src_c)
+        fig = [float(ops.point_to_plane(c, tgt_c, torch.zeros_like(c), ny, mode=1, want_grad=False)[0][1]) for c in (src_c, moved)]
+        print(f"point-to-plane residual of {src_c.shape[0]} source samples against the target samples' normals: "
+              f"before {fig[0]:.6g}  after {fig[1]:.6g}")
     if args.pull_back:
         pulled, info = model.inverse_warp(tgt_v)
         write_ply_ascii(args.pull_back, pulled.cpu().numpy(), tgt_f)

@@ -239,6 +239,10 @@ _SIGS = {
     "ndp_knn": [V, I, V, I, I, V, V, V],
     "ndp_normals_from_knn": [V, I, V, I, V, V, V, V],
     "ndp_point_to_plane": [V, I, V, I, V, V, F, V, V, V, V, I, V, V, V],
+    "ndp_rigid_fit": [V, V, V, V, V, c_int_p, I, F, V, V, V, V, V],
+    "ndp_rigid_score": [V, V, V, V, c_int_p, I, I, F, V, V, V],
+    "ndp_ransac_rigid_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_ransac_rigid": [V, V, V, c_int_p, I, V, I, F, F, I, V, V, V, V, V, V, V, V, V, V, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

@@ -357,6 +357,92 @@ def point_to_plane(x, y, nx, ny, trunc=math.inf, mode=0, nn=None, want_grad=True
     return out, gx, nn, gy
 
 
+def _rigid_problems(src, tgt, offsets):
+    """src, tgt [sum K,3] and offsets (None: one problem; else B + 1 ascending ints, host side) -> (B, device int32 tensor, ctypes
+    host copy).  The entries check the host copy; the kernels read the device one."""
+    _cloud(src, "src"); _cloud(tgt, "tgt")
+    if tgt.shape != src.shape:
+        raise ValueError(f"src and tgt must list the same correspondences, got {tuple(src.shape)} and {tuple(tgt.shape)}")
+    n = src.shape[0]
+    off = [0, n] if offsets is None else [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    if len(off) < 2 or off[0] != 0 or off[-1] != n:
+        raise ValueError(f"offsets must run from 0 to {n} in B + 1 entries, got {off[:4]}{'...' if len(off) > 4 else ''}")
+    host = (ctypes.c_int * len(off))(*off)
+    return len(off) - 1, torch.tensor(off, dtype=torch.int32).to(src.device), host
+
+
+def rigid_fit(src, tgt, w=None, mask=None, eps=1e-4, offsets=None):
+    """Weighted Procrustes (Kabsch) of correspondences src [K,3] -> tgt [K,3], the reference's arithmetic (procrustes.py:18-44) in
+    double on the device (csrc/ndp_rigid.inc: k_rigid_fit) -> (R [B,3,3], t [B,3], condition [B], status [B] int32).  w [K]: weights;
+    mask [K] uint8: non-zero rows weigh 1; neither: all ones.  offsets: B + 1 ascending row offsets for B problems in one call.
+    status 1 (fewer than 3 weighted rows, zero weight sum) or 2 (rows on a line): identity, zero, condition inf."""
+    B, off, host = _rigid_problems(src, tgt, offsets)
+    if w is not None and mask is not None:
+        raise ValueError("rigid_fit takes weights or a mask, not both")
+    if w is not None:
+        _chk(w, "w")
+        if w.numel() != src.shape[0]:
+            raise ValueError(f"w must hold {src.shape[0]} weights, got {tuple(w.shape)}")
+    if mask is not None:
+        _chk(mask, "mask", torch.uint8)
+        if mask.numel() != src.shape[0]:
+            raise ValueError(f"mask must hold {src.shape[0]} entries, got {tuple(mask.shape)}")
+    R = torch.empty(B, 3, 3, device=src.device)
+    t = torch.empty(B, 3, device=src.device)
+    cond = torch.empty(B, device=src.device)
+    status = torch.empty(B, device=src.device, dtype=torch.int32)
+    N.check(N.lib().ndp_rigid_fit(_p(src), _p(tgt), _p(w), _p(mask), _p(off), host, B, float(eps), _p(R), _p(t), _p(cond), _p(status),
+                                  N.stream_ptr(src.device)), "ndp_rigid_fit")
+    return R, t, cond, status
+
+
+def rigid_score(T, src, tgt, thr, offsets=None):
+    """Residuals of given transforms: T [B,H,12] (or [H,12] for one problem; R row-major then t) -> (count [B,H] int32 of rows with
+    |R s + t - y|^2 < thr^2, sse [B,H] the fp32 sum of those squared residuals in row order) (csrc/ndp_rigid.inc: k_rigid_score).
+    With H = 1 count / K is the reference's inlier ratio."""
+    B, off, host = _rigid_problems(src, tgt, offsets)
+    _chk(T, "T")
+    if T.ndim == 2:
+        T = T[None]
+    if T.ndim != 3 or T.shape[0] != B or T.shape[2] != 12 or T.shape[1] < 1:
+        raise ValueError(f"T must be [{B}, H, 12] with H >= 1, got {tuple(T.shape)}")
+    H = T.shape[1]
+    count = torch.empty(B, H, device=src.device, dtype=torch.int32)
+    sse = torch.empty(B, H, device=src.device)
+    N.check(N.lib().ndp_rigid_score(_p(T), _p(src), _p(tgt), _p(off), host, B, H, float(thr), _p(count), _p(sse), N.stream_ptr(src.device)),
+            "ndp_rigid_score")
+    return count, sse
+
+
+def ransac_rigid(src, tgt, triples, thr, edge_ratio=0.9, refine_iters=2, offsets=None, want_hypotheses=False):
+    """RANSAC over given hypotheses (csrc/ndp_rigid.inc): triples [B,H,3] int32 (or [H,3]) index each problem's own rows
+    (rigid.draw_triples).  -> dict(R [B,3,3], t [B,3], mask [K] uint8, count [B], rmse [B], best [B], status [B]); with
+    want_hypotheses also h_count [B,H], h_flags [B,H] (1 bad index, 2 edge length, 4 collinear) and h_T [B,H,12]."""
+    B, off, host = _rigid_problems(src, tgt, offsets)
+    _chk(triples, "triples", torch.int32)
+    if triples.ndim == 2:
+        triples = triples[None]
+    if triples.ndim != 3 or triples.shape[0] != B or triples.shape[2] != 3 or triples.shape[1] < 1:
+        raise ValueError(f"triples must be [{B}, H, 3] with H >= 1, got {tuple(triples.shape)}")
+    H, dev = triples.shape[1], src.device
+    nb = ctypes.c_longlong()
+    N.check(N.lib().ndp_ransac_rigid_workspace(B, H, ctypes.byref(nb)), "ndp_ransac_rigid_workspace")
+    ws = torch.empty(nb.value // 4, device=dev, dtype=torch.int32)
+    out = dict(R=torch.empty(B, 3, 3, device=dev), t=torch.empty(B, 3, device=dev), mask=torch.empty(src.shape[0], device=dev, dtype=torch.uint8),
+               count=torch.empty(B, device=dev, dtype=torch.int32), rmse=torch.empty(B, device=dev),
+               best=torch.empty(B, device=dev, dtype=torch.int32), status=torch.empty(B, device=dev, dtype=torch.int32))
+    hc = hf = hT = None
+    if want_hypotheses:
+        hc = torch.empty(B, H, device=dev, dtype=torch.int32)
+        hf = torch.empty(B, H, device=dev, dtype=torch.int32)
+        hT = torch.empty(B, H, 12, device=dev)
+        out.update(h_count=hc, h_flags=hf, h_T=hT)
+    N.check(N.lib().ndp_ransac_rigid(_p(src), _p(tgt), _p(off), host, B, _p(triples), H, float(thr), float(edge_ratio), int(refine_iters),
+                                     _p(ws), _p(out["R"]), _p(out["t"]), _p(out["mask"]), _p(out["count"]), _p(out["rmse"]), _p(out["best"]),
+                                     _p(out["status"]), _p(hc), _p(hf), _p(hT), N.stream_ptr(dev)), "ndp_ransac_rigid")
+    return out
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)

@@ -11,6 +11,10 @@ is outside this repository's scope.  Here they are *precom
 `(src[idx], GT-warped src[idx] + N(0, 0.005^2))`.  Everything after the matcher
 is upstream's flow: GT scene flow and overlap mask (:111-124), `load_pcds(src, tgt, landmarks=(ldmk_s, ldmk_t))`,
 `register()`, `compute_flow_metrics`, `AverageMeter`, timers.
+
+`--rigid-landmarks THR` (off by default; without it the output is unchanged) also runs RANSAC on every pair's landmarks
+(`deformationpyramid_amd/rigid.py`) and prints a `rigid-*` row -- how much of the ground-truth flow one rigid motion explains -- with
+the mean inlier ratio; `--rigid-landmarks-filter` then registers on the inlier landmarks only.
 """
 import argparse
 import os
@@ -27,7 +31,7 @@ from deformationpyramid_amd.parallel import shard_range
 from eval_nolearned import FourDMatchPairs, dist_setup, reduce_meters
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="config/LNDP.yaml", help="Path to the config file.")
     ap.add_argument("--visualize", action="store_true", help="(upstream flag; mayavi is out of scope here)")
@@ -36,7 +40,30 @@ def main():
     ap.add_argument("--synthetic", type=int, default=32, help="pairs to generate when the dataset is absent")
     ap.add_argument("--landmarks", type=str, default="", help="directory of precomputed <stem>.npz (ldmk_s, ldmk_t)")
     ap.add_argument("--K", type=int, default=500, help="synthetic landmarks per pair")
-    args = ap.parse_args()
+    ap.add_argument("--rigid-landmarks", type=float, default=0.0, metavar="THR",
+                    help="RANSAC a rigid motion through each pair's landmarks (inlier distance THR): adds a rigid-* metric row and the mean inlier ratio")
+    ap.add_argument("--rigid-landmarks-filter", action="store_true", help="with --rigid-landmarks: register on the inlier landmarks only")
+    return ap
+
+
+def rigid_rows(items, thr, keep_inliers):
+    """RANSAC on every pair's landmarks (deformationpyramid_amd/rigid.py) -> (rigid flows R src + t - src, inlier ratios, items with
+    the landmarks filtered when keep_inliers)."""
+    from deformationpyramid_amd.rigid import reject_landmarks
+    flows, ratios, out = [], [], []
+    for src, tgt, flow_gt, overlap, (ls, lt) in items:
+        mask, R, t = reject_landmarks(ls, lt, thr)
+        mask, R, t = mask.cpu(), R.cpu(), t.cpu()
+        flows.append(src @ R.T + t - src)
+        ratios.append(float(mask.float().mean()))
+        if keep_inliers and int(mask.sum()) >= 3:
+            ls, lt = ls[mask].contiguous(), lt[mask].contiguous()
+        out.append((src, tgt, flow_gt, overlap, (ls, lt)))
+    return flows, ratios, out
+
+
+def main():
+    args = make_parser().parse_args()
     world, rank, local_rank, backend = dist_setup()              # torchrun: pairs sharded over ranks (BASELINE config 5)
     setup_seed(rank)
     config = load_config(args.config, make_dirs=rank == 0, device=local_rank)
@@ -64,6 +91,9 @@ def main():
             for p in range(*shard_range(n_total, rank, world)):
                 src, tgt, flow_gt, overlap = synthetic_pair(p)
                 items.append((src, tgt, flow_gt, overlap, synthetic_landmarks(p, src, flow_gt, k=args.K)))
+        rigid_flows = None
+        if args.rigid_landmarks > 0:
+            rigid_flows, inlier_ratios, items = rigid_rows(items, args.rigid_landmarks, args.rigid_landmarks_filter)
         if args.batched:
             timer.tic("registration")
             results = model.register_batch([(s, t, l) for s, t, _, _, l in items], slots=args.slots)
@@ -90,6 +120,16 @@ def main():
             message = f"{n_total}/{n_total}: " + "".join(f"{k}: {avgs[k]:.3f}\t" for k in keys)
             Logger(os.path.join(config.snapshot_dir, benchmark + ".log")).write(message + "\n")
             print("score on ", benchmark, "\n", message)
+        if rigid_flows is not None:
+            meters = {}
+            for flow, ratio, (_, _, flow_gt, overlap, _) in zip(rigid_flows, inlier_ratios, items):
+                info = dict(compute_flow_metrics(flow, flow_gt, overlap=overlap), inlier_ratio=ratio)
+                for k, v in info.items():
+                    meters.setdefault("rigid-" + k, AverageMeter()).update(v)
+            keys, avgs = reduce_meters(meters, len(items), world, local_rank, backend)
+            if rank == 0:
+                print("rigid motion through the landmarks, thr =", args.rigid_landmarks, "\n",
+                      f"{n_total}/{n_total}: " + "".join(f"{k}: {avgs[k]:.3f}\t" for k in keys))
         if not (os.path.isdir(root) and args.landmarks):
             break
     if rank == 0:

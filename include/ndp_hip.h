@@ -305,6 +305,48 @@ int ndp_point_to_plane(const float *x, int S, const float *y, int T, const float
                        const float *d2x, const int *idx_x, const float *d2y, const int *idx_y, int mode, float *out, float *gx,
                        void *stream);
 
+/* Rigid alignment from correspondences (csrc/ndp_rigid.inc; DESIGN.md "Rigid alignment").  Batched over B independent problems:
+ * problem b owns the rows off[b] .. off[b + 1] of src [sum K][3] and tgt [sum K][3]; `off` is B + 1 device int32, `off_host` the same
+ * B + 1 values in host memory, which the entries check.  Device pointers to contiguous fp32 / int32 / uint8; nothing is allocated,
+ * no atomics, no random numbers: the same inputs give the same bits.  1 <= B <= 65535.
+ *
+ * ndp_rigid_fit: weighted Procrustes (Kabsch), the reference's arithmetic (correspondence/lepard/procrustes.py:30-43) in double:
+ *   wn = w / (sum |w| + eps), mean_X = sum wn x, mean_Y = sum wn y, Sxy = sum (y - mean_Y) (wn (x - mean_X))^T from differences,
+ *   the 3 x 3 SVD by one-sided Jacobi, R = U diag(1, 1, det U det V) V^T, t = mean_Y - R mean_X, condition = D.max / D.min (inf for
+ *   a rank-deficient Sxy).  w [sum K] fp32 or NULL; mask [sum K] uint8 (non-zero = weight 1) or NULL, not both; both NULL: all ones.
+ *   One workgroup per problem, one launch.  -> R [B][9] row-major, t [B][3], condition [B], status [B]: 0, or 1 when fewer than 3
+ *   rows have a non-zero weight or the weights sum to zero, or 2 when Sxy has rank below 2 (the rows lie on a line or coincide):
+ *   then R is the identity, t zero and the condition inf -- never NaN.  K = 0 is accepted (status 1).
+ *   NDP_E_INVALID: B outside 1..65535, off_host not monotone or negative, w and mask together, eps negative or not finite, a NULL
+ *   pointer other than w / mask.
+ * ndp_rigid_score: H transforms per problem, T [B][H][12] = R row-major then t.  Per transform count [B][H] = number of rows with
+ *   d2 < thr * thr (the product in fp32) and sse [B][H] (may be NULL) = the fp32 sum of those d2 in row order, with
+ *     d_a = fmaf(R[a][0], sx, fmaf(R[a][1], sy, fmaf(R[a][2], sz, t[a]))) - y_a,   d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)).
+ *   One lane per transform, 256 per workgroup, the rows streamed through LDS in tiles of 2048: any K >= 1.  One launch.
+ *   NDP_E_INVALID: B, off_host as above, a problem without rows, H < 1, thr not positive and finite, a NULL pointer other than sse.
+ * ndp_ransac_rigid: `triples` [B][H][3] int32, indices into the problem's own rows, drawn by the caller.  A hypothesis is refused
+ *   (flag bit 1) when two of its indices are equal or one lies outside [0, K); (2) when for one of its three edges
+ *   min(|s_a - s_b|, |y_a - y_b|) < edge_ratio * max(...) in fp32 (edge_ratio 0: no such check); (4) when its triple is collinear:
+ *   the three-point fit (ndp_rigid_fit's arithmetic with w = 1 and eps = 1e-4) has D[0] / D[1] above 1e6 -- the third singular
+ *   value of a centred triple is eps-sized rounding (its Sxy has rank 2), so the ratio that says "degenerate" is that of the
+ *   first two.  A refused hypothesis is not scored: count 0, transform identity.  The others are scored as ndp_rigid_score does.  The best hypothesis has
+ *   the largest count, the lowest index among equals.  Refinement, refine_iters >= 0 times: the mask d2 < thr^2 under the current
+ *   transform, then ndp_rigid_fit over that mask (eps = 1e-4); a mask of fewer than 3 rows or a fit with a status keeps the
+ *   transform and ends the loop.  -> R [B][9], t [B][3], mask [sum K] under the final transform, count [B] its size, rmse [B] =
+ *   sqrt(mean d2 over the mask), best [B] the hypothesis index, status [B]: 0, or 1 when no hypothesis has an inlier (R identity,
+ *   t zero, mask zero, count 0, rmse 0, best -1).  h_count [B][H], h_flags [B][H], h_T [B][H][12]: the per-hypothesis results, each
+ *   may be NULL.  ws: ndp_ransac_rigid_workspace(B, H) bytes, 4-byte aligned.  Three launches.  K >= 3 per problem, no upper limit.
+ *   NDP_E_INVALID: B, off_host as above, a problem with K < 3, H < 1, thr not positive and finite, edge_ratio outside 0..1,
+ *   refine_iters < 0, a NULL pointer other than h_count / h_flags / h_T, a misaligned workspace.                                */
+int ndp_rigid_fit(const float *src, const float *tgt, const float *w, const unsigned char *mask, const int *off, const int *off_host,
+                  int B, float eps, float *R, float *t, float *condition, int *status, void *stream);
+int ndp_rigid_score(const float *T, const float *src, const float *tgt, const int *off, const int *off_host, int B, int H, float thr,
+                    int *count, float *sse, void *stream);
+int ndp_ransac_rigid_workspace(int B, int H, long long *nbytes);
+int ndp_ransac_rigid(const float *src, const float *tgt, const int *off, const int *off_host, int B, const int *triples, int H, float thr,
+                     float edge_ratio, int refine_iters, void *ws, float *R, float *t, unsigned char *mask, int *count, float *rmse,
+                     int *best, int *status, int *h_count, int *h_flags, float *h_T, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

@@ -243,6 +243,9 @@ _SIGS = {
     "ndp_rigid_score": [V, V, V, V, c_int_p, I, I, F, V, V, V],
     "ndp_ransac_rigid_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_ransac_rigid": [V, V, V, c_int_p, I, V, I, F, F, I, V, V, V, V, V, V, V, V, V, V, V, V],
+    "ndp_feat_rowstats": [V, V, V, V, c_int_p, c_int_p, I, I, F, V, V, V, V, V, V],
+    "ndp_feat_match_workspace": [I, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_feat_match": [V, V, V, V, c_int_p, c_int_p, I, I, I, F, F, I, F, I, V, V, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

@@ -38,3 +38,4 @@
 #include "ndp_sinkhorn.inc"            // Sinkhorn divergence baseline: streamed soft-minimum step / final kernels, fixed-order loss reduce
 #include "ndp_normals.inc"             // surface normals: exact K nearest neighbours, PCA normals, point-to-plane residuals and gradient
 #include "ndp_rigid.inc"               // rigid alignment from correspondences: weighted Procrustes, residual counts, RANSAC over given triples
+#include "ndp_match.inc"               // descriptor matching: S x T row statistics on the f32 MFMA, dual-softmax / dustbin OT / mutual-NN

@@ -443,6 +443,70 @@ def ransac_rigid(src, tgt, triples, thr, edge_ratio=0.9, refine_iters=2, offsets
     return out
 
 
+FEAT_MODES = {"dual_softmax": 0, "sinkhorn": 1, "mutual_nn": 2}
+
+
+def _feat_offsets(n, offsets, name, dev):
+    off = [0, n] if offsets is None else [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    if len(off) < 2 or off[0] != 0 or off[-1] != n:
+        raise ValueError(f"{name} must run from 0 to {n} in B + 1 entries, got {off[:4]}{'...' if len(off) > 4 else ''}")
+    return torch.tensor(off, dtype=torch.int32).to(dev), (ctypes.c_int * len(off))(*off)
+
+
+def _feat_problems(a, b, offsets_a, offsets_b):
+    """a [sum S,C], b [sum T,C] and their B + 1 host-side row offsets (None: one problem) -> (B, C, device offsets a / b, host a / b)."""
+    if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.ndim != 2 or b.ndim != 2:
+        raise ValueError(f"descriptors must be tensors [rows, C], got {getattr(a, 'shape', type(a))} and {getattr(b, 'shape', type(b))}")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"both sides need the same descriptor length C, got {a.shape[1]} and {b.shape[1]}")
+    _chk(a, "a"); _chk(b, "b")
+    oa, ha = _feat_offsets(a.shape[0], offsets_a, "offsets_a", a.device)
+    ob, hb = _feat_offsets(b.shape[0], offsets_b, "offsets_b", a.device)
+    if len(ha) != len(hb):
+        raise ValueError(f"both sides must list the same problems, got {len(ha) - 1} and {len(hb) - 1}")
+    return len(ha) - 1, a.shape[1], oa, ob, ha, hb
+
+
+def feat_rowstats(a, b, alpha=1.0, v=None, e=None, offsets_a=None, offsets_b=None):
+    """Row statistics of the logits alpha <a_i, b_j> + v_j, which are never stored (csrc/ndp_match.inc: k_feat_rowstats, exact fp32 on
+    the f32-input MFMA) -> (lse [sum S], max [sum S], arg [sum S] int32: the lowest j, local to the problem, that attains max).
+    v [sum T]: a potential per column; e [B]: one extra dustbin column per problem, which enters lse only.  Exchange a and b for the
+    column statistics: a logit has the same bits either way."""
+    B, C, oa, ob, ha, hb = _feat_problems(a, b, offsets_a, offsets_b)
+    if v is not None:
+        _chk(v, "v")
+        if v.numel() != b.shape[0]:
+            raise ValueError(f"v must hold one potential per row of b ({b.shape[0]}), got {tuple(v.shape)}")
+    if e is not None:
+        _chk(e, "e")
+        if e.numel() != B:
+            raise ValueError(f"e must hold one value per problem ({B}), got {tuple(e.shape)}")
+    n, dev = a.shape[0], a.device
+    lse, mx, arg = torch.empty(n, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev, dtype=torch.int32)
+    N.check(N.lib().ndp_feat_rowstats(_p(a), _p(b), _p(oa), _p(ob), ha, hb, B, C, float(alpha), _p(v), _p(e), _p(lse), _p(mx), _p(arg),
+                                      N.stream_ptr(dev)), "ndp_feat_rowstats")
+    return lse, mx, arg
+
+
+def feat_match(fs, ft, mode="dual_softmax", temperature=0.1, bin_score=1.0, iters=3, thr=0.1, mutual=True, offsets_s=None, offsets_t=None):
+    """Matches between descriptors fs [sum S,C] and ft [sum T,C] (csrc/ndp_match.inc: ndp_feat_match, one sequence of launches) ->
+    (match_t [sum S] int32: the matched target row local to the problem or -1, conf [sum S]: the confidence of each row's best
+    column).  mode "dual_softmax" (temperature), "sinkhorn" (bin_score, iters) or "mutual_nn" (temperature is the score's scale,
+    thr may be -inf)."""
+    if mode not in FEAT_MODES:
+        raise ValueError(f"mode must be one of {sorted(FEAT_MODES)}, got {mode!r}")
+    B, C, os_, ot, hs, ht = _feat_problems(fs, ft, offsets_s, offsets_t)
+    dev = fs.device
+    nb = ctypes.c_longlong()
+    N.check(N.lib().ndp_feat_match_workspace(B, fs.shape[0], ft.shape[0], ctypes.byref(nb)), "ndp_feat_match_workspace")
+    ws = torch.empty(nb.value // 4, device=dev, dtype=torch.int32)
+    match_t, conf = torch.empty(fs.shape[0], device=dev, dtype=torch.int32), torch.empty(fs.shape[0], device=dev)
+    N.check(N.lib().ndp_feat_match(_p(fs), _p(ft), _p(os_), _p(ot), hs, ht, B, C, FEAT_MODES[mode], float(temperature), float(bin_score),
+                                   int(iters), float(thr), int(bool(mutual)), _p(ws), _p(match_t), _p(conf), N.stream_ptr(dev)),
+            "ndp_feat_match")
+    return match_t, conf
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)

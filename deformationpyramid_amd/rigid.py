@@ -46,15 +46,22 @@ def ransac_rigid(src, tgt, thr, max_iteration=50000, seed=0, edge_ratio=0.9, ref
     return ops.ransac_rigid(src, tgt, triples, thr, edge_ratio=edge_ratio, refine_iters=refine_iters)
 
 
-def ransac_pose_estimation(src_pcd, tgt_pcd, corrs, distance_threshold=0.05, ransac_n=3, max_iteration=50000, seed=0):
+def ransac_pose_estimation(src_pcd, tgt_pcd, corrs=None, distance_threshold=0.05, ransac_n=3, max_iteration=50000, seed=0, src_feat=None,
+                           tgt_feat=None):
     """The reference's helper (correspondence/lepard/loss.py:13): corrs = [s_ind, t_ind] pairs src_pcd[s_ind[i]] with tgt_pcd[t_ind[i]]
     -> the 4 x 4 pose (float64 numpy) that takes the source onto the target.  Edge-length check 0.9 and distance check at
-    distance_threshold, as there; every one of the max_iteration hypotheses is scored (no confidence-bound early exit)."""
+    distance_threshold, as there; every one of the max_iteration hypotheses is scored (no confidence-bound early exit).
+    corrs = None with src_feat [S,C] and tgt_feat [T,C]: the correspondences are the descriptors' mutual matches
+    (matching.mutual_selection), the `mutual=True` branch of utils/benchmark_utils.py:251-274."""
     if ransac_n != 3:
         raise ValueError(f"ransac_n = {ransac_n}: only ransac_n = 3 is served (a hypothesis is a three-point fit)")
+    if corrs is None and (src_feat is None or tgt_feat is None):
+        raise ValueError("ransac_pose_estimation needs corrs, or src_feat and tgt_feat to match")
     dev = _device(src_pcd, tgt_pcd)
-    s_ind = torch.as_tensor(np.asarray(corrs[0])).long().to(dev)
-    t_ind = torch.as_tensor(np.asarray(corrs[1])).long().to(dev)
+    if corrs is None:
+        from . import matching
+        corrs = matching.mutual_selection(_f32(src_feat, dev), _f32(tgt_feat, dev))
+    s_ind, t_ind = (c.long().to(dev) if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c)).long().to(dev) for c in corrs[:2])
     src, tgt = _f32(src_pcd, dev)[s_ind].contiguous(), _f32(tgt_pcd, dev)[t_ind].contiguous()
     out = ransac_rigid(src, tgt, distance_threshold, max_iteration=max_iteration, seed=seed)
     pose = np.eye(4)

@@ -67,6 +67,26 @@ def synthetic_landmarks(p, src, flow_gt, k=500, noise=0.005):
     return ls, lt
 
 
+def synthetic_descriptors(p, ls, lt, C=32, noise=0.3, impostors=0.0):
+    """Seeded descriptors planted on corresponding points ls [K,3] -> lt [K,3] (synthetic_landmarks): Gaussian rows, the target's a
+    copy plus `noise` per component, both normalised to length sqrt(C) (so <fs, ft> / C is a cosine), the target side shuffled.  A
+    share `impostors` of the target points is moved to a random place in the cloud's box while its descriptor still answers: a
+    confident wrong match, as a repeated structure gives.  -> (pts_s, pts_t, feat_s, feat_t, perm) with pts_t[k] = lt'[perm[k]]."""
+    g = torch.Generator().manual_seed(7000 + p)
+    K = ls.shape[0]
+    fs = torch.randn(K, C, generator=g)
+    ft = fs + noise * torch.randn(K, C, generator=g)
+    fs = fs / fs.norm(dim=1, keepdim=True) * C ** 0.5
+    ft = ft / ft.norm(dim=1, keepdim=True) * C ** 0.5
+    lt = lt.clone()
+    n_imp = int(K * impostors + 1e-9)
+    if n_imp:
+        lo, hi = lt.min(0).values, lt.max(0).values
+        lt[torch.randperm(K, generator=g)[:n_imp]] = lo + (hi - lo) * torch.rand(n_imp, 3, generator=g)
+    perm = torch.randperm(K, generator=g)
+    return ls.contiguous(), lt[perm].contiguous(), fs.contiguous(), ft[perm].contiguous(), perm
+
+
 def synthetic_depth_pair(seed=0, H=120, W=160):
     """Two small 16-bit depth maps (millimetres) of a bumpy surface, the second one deformed and shifted, for the embedded-
     deformation (N-ICP) baseline that starts from depth images (registration.py:38-90); a hole and a depth step exercise the

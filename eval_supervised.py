@@ -12,6 +12,9 @@ is outside this repository's scope.  Here they are *precom
 is upstream's flow: GT scene flow and overlap mask (:111-124), `load_pcds(src, tgt, landmarks=(ldmk_s, ldmk_t))`,
 `register()`, `compute_flow_metrics`, `AverageMeter`, timers.
 
+`--descriptors DIR [--match-type dual_softmax|sinkhorn|mutual_nn]` (off by default; without it the output is unchanged) matches
+the landmarks from per-point descriptors on the GPU (deformationpyramid_amd/matching.py): each `<stem>.npz` holds `pts_s, pts_t,
+feat_s, feat_t`; without the dataset seeded descriptors are planted on the synthetic pairs' landmark points.  It composes with:
 `--rigid-landmarks THR` (off by default; without it the output is unchanged) also runs RANSAC on every pair's landmarks
 (`deformationpyramid_amd/rigid.py`) and prints a `rigid-*` row -- how much of the ground-truth flow one rigid motion explains -- with
 the mean inlier ratio; `--rigid-landmarks-filter` then registers on the inlier landmarks only.
@@ -25,7 +28,7 @@ import torch
 from deformationpyramid_amd.config import load_config
 from deformationpyramid_amd.loss import compute_flow_metrics
 from deformationpyramid_amd.registration import Registration
-from deformationpyramid_amd.synthetic import synthetic_landmarks, synthetic_pair
+from deformationpyramid_amd.synthetic import synthetic_descriptors, synthetic_landmarks, synthetic_pair
 from deformationpyramid_amd.utils import AverageMeter, Logger, Timers, setup_seed
 from deformationpyramid_amd.parallel import shard_range
 from eval_nolearned import FourDMatchPairs, dist_setup, reduce_meters
@@ -43,7 +46,21 @@ def make_parser():
     ap.add_argument("--rigid-landmarks", type=float, default=0.0, metavar="THR",
                     help="RANSAC a rigid motion through each pair's landmarks (inlier distance THR): adds a rigid-* metric row and the mean inlier ratio")
     ap.add_argument("--rigid-landmarks-filter", action="store_true", help="with --rigid-landmarks: register on the inlier landmarks only")
+    ap.add_argument("--descriptors", type=str, default=None, metavar="DIR",
+                    help="match landmarks from per-point descriptors: directory of <stem>.npz (pts_s, pts_t, feat_s, feat_t); "
+                         "without the dataset, seeded descriptors planted on the synthetic pairs' landmark points")
+    ap.add_argument("--match-type", type=str, default="dual_softmax", choices=["dual_softmax", "sinkhorn", "mutual_nn"],
+                    help="with --descriptors: the matcher (deformationpyramid_amd/matching.py)")
     return ap
+
+
+def descriptor_landmarks(d, match_type):
+    """pts_s, pts_t, feat_s, feat_t -> (ldmk_s, ldmk_t) on the CPU, matched on the GPU (deformationpyramid_amd/matching.py)."""
+    from deformationpyramid_amd.matching import landmarks_from_descriptors
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ls, lt = landmarks_from_descriptors(*(torch.as_tensor(np.asarray(d[k])).float().to(dev) for k in ("pts_s", "pts_t", "feat_s", "feat_t")),
+                                        match_type=match_type)
+    return ls.cpu(), lt.cpu()
 
 
 def rigid_rows(items, thr, keep_inliers):
@@ -75,14 +92,18 @@ def main():
         config.split["test"] = benchmark
         root = os.path.join(config.data_root, benchmark)
         items = []
-        if os.path.isdir(root) and args.landmarks:
+        have_data = os.path.isdir(root) and bool(args.landmarks or args.descriptors)
+        if have_data:
             data = FourDMatchPairs(config.data_root, benchmark)
             n_total = len(data)
             for i in range(*shard_range(n_total, rank, world)):
                 src, tgt, flow_gt, overlap = data[i]
                 stem = os.path.splitext(os.path.basename(data.files[i]))[0]
-                lm = np.load(os.path.join(args.landmarks, stem + ".npz"))
-                ldmk = (torch.from_numpy(lm["ldmk_s"]).float(), torch.from_numpy(lm["ldmk_t"]).float())
+                if args.descriptors:
+                    ldmk = descriptor_landmarks(np.load(os.path.join(args.descriptors, stem + ".npz")), args.match_type)
+                else:
+                    lm = np.load(os.path.join(args.landmarks, stem + ".npz"))
+                    ldmk = (torch.from_numpy(lm["ldmk_s"]).float(), torch.from_numpy(lm["ldmk_t"]).float())
                 items.append((src, tgt, flow_gt, overlap, ldmk))
         else:
             if rank == 0:
@@ -90,7 +111,15 @@ def main():
             n_total = args.synthetic
             for p in range(*shard_range(n_total, rank, world)):
                 src, tgt, flow_gt, overlap = synthetic_pair(p)
-                items.append((src, tgt, flow_gt, overlap, synthetic_landmarks(p, src, flow_gt, k=args.K)))
+                ldmk = synthetic_landmarks(p, src, flow_gt, k=args.K)
+                if args.descriptors:
+                    ps, pt, fs, ft, _ = synthetic_descriptors(p, *ldmk)
+                    if args.match_type == "sinkhorn":               # it has no temperature: the 1 / 0.1 goes into the descriptors' length
+                        fs, ft = fs * 10 ** 0.5, ft * 10 ** 0.5
+                    ldmk = descriptor_landmarks(dict(pts_s=ps, pts_t=pt, feat_s=fs, feat_t=ft), args.match_type)
+                items.append((src, tgt, flow_gt, overlap, ldmk))
+            if rank == 0 and args.descriptors:
+                print(f"landmarks matched from descriptors ({args.match_type}): {sum(l[4][0].shape[0] for l in items) / max(len(items), 1):.1f} per pair")
         rigid_flows = None
         if args.rigid_landmarks > 0:
             rigid_flows, inlier_ratios, items = rigid_rows(items, args.rigid_landmarks, args.rigid_landmarks_filter)
@@ -130,7 +159,7 @@ def main():
             if rank == 0:
                 print("rigid motion through the landmarks, thr =", args.rigid_landmarks, "\n",
                       f"{n_total}/{n_total}: " + "".join(f"{k}: {avgs[k]:.3f}\t" for k in keys))
-        if not (os.path.isdir(root) and args.landmarks):
+        if not have_data:
             break
     if rank == 0:
         print("time cost average")

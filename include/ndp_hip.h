@@ -347,6 +347,38 @@ int ndp_ransac_rigid(const float *src, const float *tgt, const int *off, const i
                      float edge_ratio, int refine_iters, void *ws, float *R, float *t, unsigned char *mask, int *count, float *rmse,
                      int *best, int *status, int *h_count, int *h_flags, float *h_T, void *stream);
 
+/* Descriptor matching (csrc/ndp_match.inc; DESIGN.md "Descriptor matching"; since ABI 212).  Batched over B independent problems:
+ * problem b owns the rows offA[b] .. offA[b + 1] of A [sum S][C] and offB[b] .. offB[b + 1] of B [sum T][C], row-major fp32; the
+ * `off*` are B + 1 device int32, the `off*_host` the same values in host memory, which the entries check.  The S x T matrix is
+ * never stored.  Nothing is allocated, no atomics: the same inputs give the same bits.  1 <= B <= 65535, 1 <= C <= 1056, every
+ * problem has S >= 1 and T >= 1.
+ *
+ * ndp_feat_rowstats: with a_ij = alpha * <A_i, B_j> + v_j (the dot product a k-ascending fp32 fma chain on the f32-input MFMA,
+ *   the same bits with A and B exchanged), per row i of A:
+ *     lse [sum S] = log(sum_j exp(a_ij) [+ exp(e[b])]),  max [sum S] = max_j a_ij,  arg [sum S] = the lowest j (local to the
+ *   problem, int32) that attains it.  v [sum T] (per-column potential) and e [B] (one extra "dustbin" column per problem, which
+ *   enters lse only) are device arrays or NULL; each of lse / max / arg may be NULL, not all three.  One launch.  Column
+ *   statistics: call it with A and B (and their offsets) exchanged.
+ *   NDP_E_INVALID: B, C, offsets as above (not monotone, negative, an empty side), a NULL or misaligned pointer, alpha not finite.
+ * ndp_feat_match: per source row match_t [sum S] (the target index local to the problem, or -1) and conf [sum S] (the confidence
+ *   of the row's best column, matched or not).  Row i matches j = arg_row[i] iff conf > thr and (mutual != 0: arg_col[j] == i).
+ *   mode 0, dual_softmax (correspondence/lepard/matching.py:144-157): s = <fs_i, ft_j> / (C * temperature),
+ *     conf_ij = softmax_i(s) softmax_j(s) = exp(2 s_ij - lse_row_i - lse_col_j); four row-statistics launches.
+ *   mode 1, sinkhorn (matching.py:6-38, 159-170) on the unpadded problem: s = <fs_i, ft_j> / C augmented by a dustbin row and
+ *     column of score bin_score, `iters` iterations from u = v = 0, conf = exp(s + u + v + log(S + T)); 2 iters + 1 row-statistics
+ *     launches (2 at iters = 0).  `temperature` is not read.
+ *   mode 2, mutual_nn (utils/benchmark_utils.py:335-359): the raw scores `temperature` * <fs_i, ft_j> (pass 1), conf = the score;
+ *     thr may be -inf.
+ *   ws: ndp_feat_match_workspace(B, sum S, sum T) bytes, 4-byte aligned.  All launches go to `stream` in order.
+ *   NDP_E_INVALID: as ndp_feat_rowstats, a mode outside 0..2, temperature not positive and finite (modes 0, 2), bin_score not
+ *   finite (mode 1), iters < 0, thr NaN.                                                                                        */
+int ndp_feat_rowstats(const float *A, const float *B_rows, const int *offA, const int *offB, const int *offA_host, const int *offB_host,
+                      int B, int C, float alpha, const float *v, const float *e, float *lse, float *max, int *arg, void *stream);
+int ndp_feat_match_workspace(int B, long long nS, long long nT, long long *nbytes);
+int ndp_feat_match(const float *fs, const float *ft, const int *offS, const int *offT, const int *offS_host, const int *offT_host,
+                   int B, int C, int mode, float temperature, float bin_score, int iters, float thr, int mutual, void *ws,
+                   int *match_t, float *conf, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

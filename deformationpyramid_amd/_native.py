@@ -246,6 +246,10 @@ _SIGS = {
     "ndp_feat_rowstats": [V, V, V, V, c_int_p, c_int_p, I, I, F, V, V, V, V, V, V],
     "ndp_feat_match_workspace": [I, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_feat_match": [V, V, V, V, c_int_p, c_int_p, I, I, I, F, F, I, F, I, V, V, V, V],
+    "ndp_voxel_subsample_workspace": [ctypes.c_longlong, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_voxel_subsample": [V, V, I, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, c_int_p, V],
+    "ndp_radius_search_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_radius_search": [V, V, c_int_p, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

@@ -39,3 +39,4 @@
 #include "ndp_normals.inc"             // surface normals: exact K nearest neighbours, PCA normals, point-to-plane residuals and gradient
 #include "ndp_rigid.inc"               // rigid alignment from correspondences: weighted Procrustes, residual counts, RANSAC over given triples
 #include "ndp_match.inc"               // descriptor matching: S x T row statistics on the f32 MFMA, dual-softmax / dustbin OT / mutual-NN
+#include "ndp_kpconv.inc"              // KPConv inputs: voxel barycentre subsampling and fixed-radius neighbours on a sorted cell-key table

@@ -507,6 +507,102 @@ def feat_match(fs, ft, mode="dual_softmax", temperature=0.1, bin_score=1.0, iter
     return match_t, conf
 
 
+RADIUS_MAX_K = 64
+
+
+def _stack_lengths(lengths, n, name):
+    """lengths (tensor, array or list, every entry >= 1, summing to n) -> ctypes int array for the C entries."""
+    ls = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if not ls or min(ls) < 1:
+        raise ValueError(f"{name}: every cloud needs at least one point, got lengths {ls[:8]}{'...' if len(ls) > 8 else ''}")
+    if sum(ls) != n:
+        raise ValueError(f"{name} must sum to the number of stacked points ({n}), got {sum(ls)}")
+    if len(ls) > 65535:
+        raise ValueError(f"{name}: at most 65535 clouds in a batch, got {len(ls)}")
+    return (ctypes.c_int * len(ls))(*ls)
+
+
+def _stacked(t, name):
+    if not isinstance(t, torch.Tensor) or t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{name} must be a [N, 3] tensor with N >= 1, got {getattr(t, 'shape', type(t))}")
+    return t
+
+
+def voxel_subsample(points, lengths, dl, features=None, max_p=0):
+    """Voxel-grid barycentre subsampling of stacked clouds (csrc/ndp_kpconv.inc: k_voxel_keys, sort, k_voxel_reduce) ->
+    (s_points [M,3], s_lengths [B] int32 on the host, s_features [M,F] or None, inverse [N] int32: the output row of every input
+    point, -1 where max_p dropped its voxel).  Voxel membership is the reference's fp32 expression; a barycentre is a float64 sum in
+    input order rounded once; output order per cloud is ascending (iz, iy, ix); max_p > 0 keeps the first max_p voxels per cloud.
+    Class labels (the reference's majority vote) are not served.  Synchronises: the output size is data."""
+    _stacked(points, "points")
+    n, dl = points.shape[0], float(dl)
+    hl = _stack_lengths(lengths, n, "lengths")
+    if not (dl > 0 and math.isfinite(dl)):
+        raise ValueError(f"dl must be positive and finite, got {dl}")
+    F = 0
+    if features is not None:
+        if not isinstance(features, torch.Tensor) or features.ndim != 2 or features.shape[0] != n or features.shape[1] < 1:
+            raise ValueError(f"features must be [N, F] with N = {n} and F >= 1, got {getattr(features, 'shape', type(features))}")
+        F = features.shape[1]
+    _chk(points, "points")
+    if features is not None:
+        _chk(features, "features")
+    B, dev = len(hl), points.device
+    nb = ctypes.c_longlong()
+    N.check(N.lib().ndp_voxel_subsample_workspace(n, B, ctypes.byref(nb)), "ndp_voxel_subsample_workspace")
+    ws = torch.empty((nb.value + 15) // 16 * 4, device=dev, dtype=torch.int32)
+    out = torch.empty(n, 3, device=dev)
+    out_f = torch.empty(n, F, device=dev) if F else None
+    inverse = torch.empty(n, device=dev, dtype=torch.int32)
+    out_len = (ctypes.c_int * B)()
+    N.check(N.lib().ndp_voxel_subsample(_p(points), _p(features), F, hl, B, dl, int(max_p), _p(ws), nb.value, _p(out), _p(out_f), _p(inverse),
+                                        out_len, N.stream_ptr(dev)), "ndp_voxel_subsample")
+    m = sum(out_len)
+    return out[:m], torch.tensor(list(out_len), dtype=torch.int32), (out_f[:m] if F else None), inverse
+
+
+def radius_search(q, s, q_lengths, s_lengths, radius, max_neighbors, want_d2=False):
+    """Fixed-radius neighbours of stacked queries among the supports of their own cloud (csrc/ndp_kpconv.inc: k_radius_grid, sort,
+    k_radius_search) -> (idx [Nq,K] int32, counts [Nq] int32[, d2 [Nq,K]]).  A support is listed iff d2 < radius^2 (fp32, strict, the
+    chain of ops.knn); a row holds the K = max_neighbors nearest in (d2, index) order, stacked-global indices, padded with the shadow
+    index Ns (d2: +inf); counts is the number within the radius before the cut.  max_neighbors <= 0: all of them -- K is the largest
+    count, which must not exceed 64 (see kpconv.radius_count for the counts alone).  max_neighbors = None: counts only, idx is None."""
+    _stacked(q, "q"); _stacked(s, "s")
+    nq, ns, radius = q.shape[0], s.shape[0], float(radius)
+    hq, hs = _stack_lengths(q_lengths, nq, "q_lengths"), _stack_lengths(s_lengths, ns, "s_lengths")
+    if len(hq) != len(hs):
+        raise ValueError(f"queries and supports must list the same clouds, got {len(hq)} and {len(hs)}")
+    if not (radius > 0 and math.isfinite(radius)):
+        raise ValueError(f"radius must be positive and finite, got {radius}")
+    if max_neighbors is not None and int(max_neighbors) > RADIUS_MAX_K:
+        raise ValueError(f"max_neighbors must not exceed {RADIUS_MAX_K}, got {max_neighbors}")
+    _chk(q, "q"); _chk(s, "s")
+    B, dev = len(hq), q.device
+    nb = ctypes.c_longlong()
+    N.check(N.lib().ndp_radius_search_workspace(nq, ns, B, ctypes.byref(nb)), "ndp_radius_search_workspace")
+    ws = torch.empty((nb.value + 15) // 16 * 4, device=dev, dtype=torch.int32)
+    counts = torch.empty(nq, device=dev, dtype=torch.int32)
+
+    def run(K, idx, d2):
+        N.check(N.lib().ndp_radius_search(_p(q), _p(s), hq, hs, B, radius, K, _p(ws), nb.value, _p(idx), _p(d2), _p(counts),
+                                          N.stream_ptr(dev)), "ndp_radius_search")
+
+    K = 0 if max_neighbors is None else int(max_neighbors)
+    if K <= 0:
+        run(0, None, None)
+        if max_neighbors is None:
+            return (None, counts, None) if want_d2 else (None, counts)
+        K = int(counts.max().item())
+        if K > RADIUS_MAX_K:
+            raise N.NdpError(f"radius_search: max_neighbors <= 0 asks for every neighbour, and the fullest neighbourhood holds {K} > "
+                             f"{RADIUS_MAX_K}: pass a limit, or read the sizes with kpconv.radius_count")
+    idx = torch.empty(nq, K, device=dev, dtype=torch.int32)
+    d2 = torch.empty(nq, K, device=dev) if want_d2 else None
+    if K > 0:
+        run(K, idx, d2)
+    return (idx, counts, d2) if want_d2 else (idx, counts)
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)

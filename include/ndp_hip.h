@@ -379,6 +379,36 @@ int ndp_feat_match(const float *fs, const float *ft, const int *offS, const int 
                    int B, int C, int mode, float temperature, float bin_score, int iters, float thr, int mutual, void *ws,
                    int *match_t, float *conf, void *stream);
 
+/* KPConv inputs (csrc/ndp_kpconv.inc; DESIGN.md "KPConv inputs"), ABI 213.  Stacked clouds: points [N][3] fp32 on the device and
+ * B lengths, every one >= 1, their sum N, in HOST memory.  The grid of both operators is a sorted table of 64-bit cell keys
+ * (cloud : 16 | iz : 16 | iy : 16 | ix : 16), sorted inside the library: memory is O(N) whatever the bounding box, a cloud never
+ * sees another cloud's points, there are no floating-point atomics, and the same inputs give the same bits.  BOTH ENTRIES END IN
+ * A SYNCHRONISE of `stream`: the size of the subsampled cloud is data, and so are the refusals below.
+ *
+ * ndp_voxel_subsample: barycentres of the occupied voxels of edge dl (batch_grid_subsampling, cpp_subsampling/grid_subsampling.cpp).
+ *   Membership is the reference's in fp32: origin = floorf(min * (1 / dl)) * dl per cloud, i = floorf((p - origin) / dl) per axis.
+ *   A barycentre is the sum of the voxel's points in ascending input index in double, divided by the count, rounded to fp32 once;
+ *   feat [N][F] (F >= 0, NULL at F = 0) is averaged the same way.  Output order: per cloud ascending (iz, iy, ix); max_p > 0 keeps
+ *   the first max_p voxels of each cloud.  out_pts [N][3] / out_feat [N][F] are sized for the worst case and filled for the first
+ *   sum(out_lengths_host) rows; out_lengths_host [B] (HOST) receives the voxels kept per cloud; inverse [N] (may be NULL) the output
+ *   row of every input point, -1 for a point of a voxel that max_p dropped.
+ * ndp_radius_search: for every query the supports of its own cloud with d2 < radius * radius (strict; fp32; d2 is ndp_knn's chain
+ *   of d = q - s), nearest first.  idx [nq][K] stacked-global support indices in (d2, index) order, padded with the shadow index
+ *   ns = sum of the supports' lengths; d2 [nq][K] (may be NULL) the distances, padded with +inf; counts [nq] the number within the
+ *   radius BEFORE the cut to K.  0 <= K <= 64; K = 0 fills counts only (idx may be NULL).  Queries may lie outside the supports'
+ *   bounding box.
+ * ws: at least ndp_*_workspace(...) bytes, 16-byte aligned; ws_bytes is checked.  The workspace queries need no device.
+ *   NDP_E_INVALID: B outside 1..65535, a length < 1, dl or radius not positive and finite, K outside 0..64, a NULL pointer, a
+ *   workspace too small or misaligned, a coordinate that is NaN or infinite.  NDP_E_UNSUPPORTED: more than 2^30 points, or a
+ *   cloud that spans more than 65535 cells along an axis (voxels of edge dl; cells of edge 1.03125 * radius): it does not fit
+ *   the key.                                                                                                                       */
+int ndp_voxel_subsample_workspace(long long n, int B, long long *nbytes);
+int ndp_voxel_subsample(const float *pts, const float *feat, int F, const int *lengths_host, int B, float dl, int max_p, void *ws,
+                        long long ws_bytes, float *out_pts, float *out_feat, int *inverse, int *out_lengths_host, void *stream);
+int ndp_radius_search_workspace(long long nq, long long ns, int B, long long *nbytes);
+int ndp_radius_search(const float *q, const float *s, const int *q_lengths_host, const int *s_lengths_host, int B, float radius, int K,
+                      void *ws, long long ws_bytes, int *idx, float *d2, int *counts, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

@@ -3,7 +3,7 @@
 euler deformation pyramid fitted between two meshes, then applied to every vertex of the source mesh.
 
     python shape_transfer.py -s sim3_demo/AlienSoldier.ply -t sim3_demo/Ortiz.ply [-o warped.ply]
-                             [--jacobian-stats] [--pull-back pulled.ply] [--plane-stats]
+                             [--jacobian-stats] [--pull-back pulled.ply] [--plane-stats] [--voxel-size DL]
 
 Same hard-wired settings as upstream (:27-52): 6000 surface samples per mesh, ALL of them used as Chamfer samples,
 m = 9, k0 = -8, lr 0.01, 500 iterations with the early-stop rule, Sim3 + euler; like upstream the target mean is
@@ -16,6 +16,8 @@ the mesh vertices (local volume change; det J <= 0 marks where the field folded 
 vertices into the source frame through the inverse warp (Registration.inverse_warp) and writes them with the target's faces,
 --plane-stats prints the mean point-to-plane residual |(x - p) . n| of the source samples against the target samples and their face
 normals before and after the fit (both clouds centred as the fit sees them): a quality figure that needs no ground truth.
+--voxel-size DL fits on the voxel-grid barycentres (edge DL) of the two meshes' vertices instead of the surface samples -- an even
+cover whatever the tessellation -- and still warps every source vertex; without it nothing changes.
 """
 import argparse
 
@@ -31,14 +33,6 @@ from deformationpyramid_amd.utils import setup_seed
 setup_seed(0)
 
 if __name__ == "__main__":
-    config = Config({
-        "gpu_mode": True, "deformation_model": "NDP",
-        "iters": 500, "lr": 0.01, "max_break_count": 15, "break_threshold_ratio": 0.001,
-        "samples": 6000, "motion_type": "Sim3", "rotation_format": "euler",
-        "m": 9, "k0": -8, "depth": 3, "width": 128, "act_fn": "relu",
-        "w_reg": 0, "w_ldmk": 0, "w_cd": 0.1,
-    })
-    config.device = torch.cuda.current_device()
     ap = argparse.ArgumentParser()
     ap.add_argument("-s", type=str, required=True, help="Path to the src mesh.")
     ap.add_argument("-t", type=str, required=True, help="Path to the tgt mesh.")
@@ -48,13 +42,32 @@ if __name__ == "__main__":
                     help="write the target mesh's vertices mapped into the source frame (inverse warp) here (ASCII PLY)")
     ap.add_argument("--plane-stats", action="store_true",
                     help="print the mean point-to-plane residual of the source samples against the target samples' normals before and after the fit")
+    ap.add_argument("--voxel-size", type=float, default=0.0, metavar="DL",
+                    help="fit on the voxel barycentres (edge DL, ops.voxel_subsample) of both meshes' vertices instead of 6000 surface "
+                         "samples per mesh; every vertex of the source is still warped (default 0: off)")
     args = ap.parse_args()
+    if args.voxel_size < 0:
+        ap.error("--voxel-size must be positive (0: off)")
+    config = Config({
+        "gpu_mode": True, "deformation_model": "NDP",
+        "iters": 500, "lr": 0.01, "max_break_count": 15, "break_threshold_ratio": 0.001,
+        "samples": 6000, "motion_type": "Sim3", "rotation_format": "euler",
+        "m": 9, "k0": -8, "depth": 3, "width": 128, "act_fn": "relu",
+        "w_reg": 0, "w_ldmk": 0, "w_cd": 0.1,
+    })
+    config.device = torch.cuda.current_device()
 
     rng = np.random.default_rng(0)
     src_v, src_f = read_ply_ascii(args.s)
     tgt_v, tgt_f = read_ply_ascii(args.t)
     src_pcd = sample_surface(src_v, src_f, config.samples, rng)
     tgt_pcd, tgt_nrm = sample_surface(tgt_v, tgt_f, config.samples, rng, return_normals=True)     # (the same draws and points as without)
+    if args.voxel_size > 0:
+        if args.plane_stats:
+            ap.error("--plane-stats needs the surface samples' normals: not together with --voxel-size")
+        thin = lambda v: ops.voxel_subsample(torch.from_numpy(np.ascontiguousarray(v, np.float32)).cuda(), [len(v)], args.voxel_size)[0].cpu().numpy()
+        src_pcd, tgt_pcd = thin(src_v), thin(tgt_v)
+        print("fitting on", len(src_pcd), "and", len(tgt_pcd), "voxel barycentres of", len(src_v), "and", len(tgt_v), "vertices")
 
     model = Registration(config)
     model.load_pcds(src_pcd, tgt_pcd)

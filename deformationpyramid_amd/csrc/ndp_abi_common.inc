@@ -1,4 +1,5 @@
-// ndp_abi_common.inc -- what every host entry uses (host-only): g_err / fail / hip_fail / HIP_TRY, check_desc, aligned16, set_smem;
+// ndp_abi_common.inc -- what every host entry uses (host-only): g_err / fail / failf / hip_fail / HIP_TRY, check_desc, aligned16,
+// check_batch / check_offsets (the batched entries' host-side offsets), set_smem;
 // and the entries about the library itself: ndp_version, ndp_last_error, ndp_build_id, ndp_abi_sizes.  Behind ndp_generic.inc
 // (check_desc asks gen_supported), ahead of the first file that carries host entries of its own.
 // ------------------------------------------------------------------------------------------------
@@ -7,6 +8,13 @@
 static thread_local char g_err[256] = "";
 static int fail(int code, const char *msg) {
     snprintf(g_err, sizeof g_err, "%s", msg);
+    return code;
+}
+__attribute__((format(printf, 2, 3))) static int failf(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
     return code;
 }
 static int hip_fail(hipError_t e, const char *what) {
@@ -29,6 +37,31 @@ static int check_desc(const ndp_layer_desc *d) {
     return 0;
 }
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The batched entries (rigid, matching, KPConv inputs) take B problems as rows of stacked arrays, described by a HOST array the
+// entry checks before anything is launched (the kernels read a device copy).  check_batch: B in 1..NDP_MAX_B (a grid dimension, and
+// the 16 bits of cloud in KPConv's cell key) and the host array present.  check_offsets: that, and off_host [B + 1] starts at 0 or
+// above, is monotone, and gives every problem at least min_rows rows -- `rows` is the entry's name for them in the message.
+// max_rows (may be NULL): the largest problem.
+#define NDP_MAX_B 65535
+static int check_batch(const char *who, const void *host_array, int B) {
+    if (B < 1 || B > NDP_MAX_B) return failf(NDP_E_INVALID, "%s: B must lie in 1..%d", who, NDP_MAX_B);
+    if (!host_array) return failf(NDP_E_INVALID, "%s: null pointer", who);
+    return 0;
+}
+static int check_offsets(const char *who, const int *off_host, int B, int min_rows, const char *rows, int *max_rows) {
+    if (int rc = check_batch(who, off_host, B)) return rc;
+    if (off_host[0] < 0) return failf(NDP_E_INVALID, "%s: offsets must start at 0 or above", who);
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        if (off_host[b + 1] < off_host[b]) return failf(NDP_E_INVALID, "%s: offsets must be monotone", who);
+        const int k = off_host[b + 1] - off_host[b];
+        if (k < min_rows) return failf(NDP_E_INVALID, "%s: every problem needs %s >= %d (problem %d has %d)", who, rows, min_rows, b, k);
+        mx = std::max(mx, k);
+    }
+    if (max_rows) *max_rows = mx;
+    return 0;
+}
 
 static int set_smem(const void *fn, int bytes) {
     static thread_local const void *done[32];

@@ -4,6 +4,9 @@
 // backward, written op-for-op like the CPU oracle (oracle/ndp_oracle.c) so that the two agree
 // to the last bits the transcendental functions allow.  The file is compiled with
 // -ffp-contract=off: every fused multiply-add is an explicit fmaf.
+// Below the head math: block_fold / block_fold_one, the fixed-order block-wide tree fold of the operator kernels (sums, maxima, best
+// counts), and jacobi_cs, the rotation of the two 3 x 3 Jacobi solvers (normals, rigid).  DESIGN.md section 3 lists the trees that stay
+// apart (k_kp_bounds, k_point_to_plane, k_rigid_score, the engine tick's block_sum_256_t) and why.
 //
 // Reference: model/nets.py:111-161 (NDPLayer.forward, get_Rotation), model/rigid_body.py:19-56
 // (euler_to_SO3), :89-119 (skew, exp_so3).
@@ -361,19 +364,58 @@ __device__ __forceinline__ void head_warp_bwd(const HeadCfg &hc, const float *x,
         if (a < hc.n_rot) d_o[a] = dr[a];
 }
 
-// deterministic block-wide sum (256 threads); every thread gets the result
-__device__ __forceinline__ float block_sum_256(float v, float *scratch /* >= 256 floats */) {
+// THE block-wide fold: the one fixed tree behind "every sum one fixed order".  Each of the NT threads of the workgroup brings NV
+// values; value i of thread t goes to scratch[i * NT + t], the levels s = NT / 2 .. 1 form a[t] = op(a[t], a[t + s]) with one
+// barrier per level for all NV values, and every thread receives the NV results.  The closing barrier lets scratch [NV][NT] be
+// reused at once.  The result depends on the values and on op alone, never on which lane ran when.
+template <int NV, int NT = 256, class T, class Op>
+__device__ __forceinline__ void block_fold(T (&v)[NV], T *scratch, Op op) {
     const int t = threadIdx.x;
-    scratch[t] = v;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) scratch[i * NT + t] = v[i];
     __syncthreads();
 #pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) scratch[t] = scratch[t] + scratch[t + s];
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) scratch[i * NT + t] = op(scratch[i * NT + t], scratch[i * NT + t + s]);
+        }
         __syncthreads();
     }
-    const float r = scratch[0];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = scratch[i * NT];
     __syncthreads();
-    return r;
+}
+template <int NT = 256, class T, class Op>
+__device__ __forceinline__ T block_fold_one(T v, T *scratch, Op op) {  // one value per thread: block_fold<1, NT>
+    T a[1] = {v};
+    block_fold<1, NT>(a, scratch, op);
+    return a[0];
+}
+struct FoldSum {
+    template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct FoldMax {
+    __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
+};
+// a count and the index it belongs to: the largest count wins, the lowest index among equals
+struct CountIdx {
+    int count, idx;
+};
+struct FoldBestCount {
+    __device__ __forceinline__ CountIdx operator()(CountIdx a, CountIdx b) const {
+        return (b.count > a.count || (b.count == a.count && b.idx < a.idx)) ? b : a;
+    }
+};
+
+// The Jacobi rotation that annihilates the pivot of a symmetric 2 x 2 block (two-sided) or makes two columns orthogonal
+// (one-sided), in double: theta = (a_qq - a_pp) / (2 a_pq) -> c, s; returns t = tan of the rotation angle, the smaller root.
+// (An overflow of theta to inf gives t = 0: no rotation, as it should.)
+__device__ __forceinline__ double jacobi_cs(double theta, double &c, double &s) {
+    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    c = 1.0 / sqrt(tt * tt + 1.0);
+    s = tt * c;
+    return tt;
 }
 
 // Per-point head backward for the level kernels: recompute the head stage from the saved scaled head

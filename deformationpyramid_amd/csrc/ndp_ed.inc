@@ -81,7 +81,7 @@ k_ed_arap(const float *nodes, const float *R, const float *t, const int *edges, 
         ed_edge_residual(nodes, R, t, i, j, r, dg);
         s += ew[idx] * ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
     }
-    const float tot = block_sum_256(s, red);
+    const float tot = block_fold_one(s, red, FoldSum());
     if (threadIdx.x == 0) out[0] = tot / (float)(n * K);
 }
 
@@ -133,7 +133,7 @@ k_ed_grad(const float *x, const int *anchors, const float *weights, const float 
     }
     float tot[12];
 #pragma unroll
-    for (int q = 0; q < 12; ++q) tot[q] = block_sum_256(acc[q], red);
+    for (int q = 0; q < 12; ++q) tot[q] = block_fold_one(acc[q], red, FoldSum());
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {                                    // dL/dphi_k = <dL/dR, dR/dphi_k>: one forward-mode pass per component

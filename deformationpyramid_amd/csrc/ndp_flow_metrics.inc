@@ -27,14 +27,8 @@ k_flow_metrics(const float *flow, const float *gt, const unsigned char *overlap,
     }
     for (int s = 0; s < 3; ++s)
         for (int k = 0; k < 5; ++k) {
-            red[threadIdx.x] = acc[s][k];
-            __syncthreads();
-            for (int d = 512; d > 0; d >>= 1) {
-                if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-                __syncthreads();
-            }
-            if (threadIdx.x == 0) out[5 * s + k] = red[0];
-            __syncthreads();
+            const double tot = block_fold_one<1024>(acc[s][k], red, FoldSum());
+            if (threadIdx.x == 0) out[5 * s + k] = tot;
         }
 }
 

@@ -4,8 +4,10 @@
 // entries that launch only them live together, entries that choose between files are in ndp_abi.inc.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (explicit fmaf only).
-#include "ndp_device.h"                // per-point head math (rotations, SE3 / Sim3 / sflow warp and its backward) shared by every file below
+#include "ndp_device.h"                // shared by every file below: per-point head math (rotations, warp and its backward), block_fold, jacobi_cs
 
+#include <algorithm>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
@@ -25,7 +27,7 @@
 #include "ndp_bwd_fused.inc"           // both backward layers in one launch: k_eng_bwd_f
 #include "ndp_eng_update.inc"          // engine update stage: partial fold, Adam, level hand-over (k_eng_update, k_eng_update_rest)
 #include "ndp_generic.inc"             // level kernels for every width / depth other than 128 / 3
-#include "ndp_abi_common.inc"          // host only: error string, HIP_TRY, check_desc, set_smem; ndp_version, ndp_build_id, ndp_abi_sizes
+#include "ndp_abi_common.inc"          // host only: error string, HIP_TRY, check_desc, check_batch / check_offsets, set_smem; ndp_version, ndp_build_id, ndp_abi_sizes
 #include "ndp_nsfp.inc"                // NSFP baseline: kernels, ndp_nsfp_fwd / _bwd
 #include "ndp_eng_load.inc"            // pair preparation and slot (re)fill: k_pair_means*, LoadJobs, k_eng_load
 #include "ndp_nn_cells.inc"            // exact grid ball search (behind LoadJobs: its grid-build kernel rides behind k_eng_load)

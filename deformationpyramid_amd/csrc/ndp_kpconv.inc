@@ -40,7 +40,6 @@
 #include <vector>
 
 #define KP_MAX_CELL 65535              // largest stored cell field (16 bits per axis)
-#define KP_MAX_B 65535
 #define KP_MAX_K 64
 #define KP_MAX_POINTS (1 << 30)
 #define KP_MAX_F 4096
@@ -303,16 +302,15 @@ struct KpCarve {                       // 16-byte aligned pieces of a workspace,
     }
 };
 
+// lengths [B] on the host -> offsets [B + 1] and their total, which may not exceed n_max
 static int kp_check_lengths(const char *who, const int *len, int B, long long n_max, long long *n_out, std::vector<int> *off) {
-    static thread_local char msg[160];
-    if (B < 1 || B > KP_MAX_B) { snprintf(msg, sizeof msg, "%s: B must lie in 1..%d (the cell key holds 16 bits of cloud)", who, KP_MAX_B); return fail(NDP_E_INVALID, msg); }
-    if (!len) { snprintf(msg, sizeof msg, "%s: null lengths", who); return fail(NDP_E_INVALID, msg); }
+    if (int rc = check_batch(who, len, B)) return rc;
     long long n = 0;
     off->assign(1, 0);
     for (int b = 0; b < B; ++b) {
-        if (len[b] < 1) { snprintf(msg, sizeof msg, "%s: every length must be >= 1 (cloud %d has %d)", who, b, len[b]); return fail(NDP_E_INVALID, msg); }
+        if (len[b] < 1) return failf(NDP_E_INVALID, "%s: every length must be >= 1 (cloud %d has %d)", who, b, len[b]);
         n += len[b];
-        if (n > n_max) { snprintf(msg, sizeof msg, "%s: at most %lld points in all", who, n_max); return fail(NDP_E_UNSUPPORTED, msg); }
+        if (n > n_max) return failf(NDP_E_UNSUPPORTED, "%s: at most %lld points in all", who, n_max);
         off->push_back((int)n);
     }
     *n_out = n;
@@ -370,7 +368,7 @@ struct KpVoxelWs {
 };
 
 extern "C" int ndp_voxel_subsample_workspace(long long n, int B, long long *nbytes) {
-    if (n < 1 || n > KP_MAX_POINTS || B < 1 || B > KP_MAX_B || B > n || !nbytes)
+    if (n < 1 || n > KP_MAX_POINTS || B < 1 || B > NDP_MAX_B || B > n || !nbytes)
         return fail(NDP_E_INVALID, "ndp_voxel_subsample_workspace: 1 <= B <= 65535, B <= n <= 2^30, nbytes not NULL");
     *nbytes = KpVoxelWs(nullptr, n, B).total;
     return 0;
@@ -438,7 +436,7 @@ struct KpRadiusWs {
 };
 
 extern "C" int ndp_radius_search_workspace(long long nq, long long ns, int B, long long *nbytes) {
-    if (nq < 1 || ns < 1 || nq > KP_MAX_POINTS || ns > KP_MAX_POINTS || B < 1 || B > KP_MAX_B || B > nq || B > ns || !nbytes)
+    if (nq < 1 || ns < 1 || nq > KP_MAX_POINTS || ns > KP_MAX_POINTS || B < 1 || B > NDP_MAX_B || B > nq || B > ns || !nbytes)
         return fail(NDP_E_INVALID, "ndp_radius_search_workspace: 1 <= B <= 65535, B <= nq, ns <= 2^30, nbytes not NULL");
     *nbytes = KpRadiusWs(nullptr, nq, ns, B).total;
     return 0;

@@ -2,7 +2,8 @@
 // the 1-D kernels around it (k_feat_neg, k_feat_ot_init, k_feat_ot_update, k_feat_match_finish), and ndp_feat_rowstats /
 // ndp_feat_match_workspace / ndp_feat_match, which compose dual-softmax, dustbin optimal transport and mutual nearest neighbours
 // from them.  DESIGN.md "Descriptor matching".  fp32 throughout, no atomics, every output element has one writer and every sum one
-// fixed order.  All entries are batched: problem b owns the rows offA[b] .. offA[b + 1] of A and offB[b] .. offB[b + 1] of B.
+// fixed order.  All entries are batched: problem b owns the rows offA[b] .. offA[b + 1] of A and offB[b] .. offB[b + 1] of B; the
+// entries check the host's copies of both with check_offsets (ndp_abi_common.inc).
 // ------------------------------------------------------------------------------------------------
 // k_feat_rowstats.  a_ij = alpha * <A_i, B_j> + v_j.  A workgroup (4 waves) owns FM_BM = 32 rows of A and walks the columns in
 // tiles of FM_BN = 256; wave w owns the columns 64 w .. 64 w + 63 of a tile as two 32 x 32 accumulators.  The product is taken
@@ -190,28 +191,15 @@ k_feat_rowstats_v4(const float *A, const float *Bm, const int *offA, const int *
 
 // ------------------------------------------------------------------------------------------------
 // 1-D kernels.  fm_block_lse: log-sum-exp of x[0 .. n) and one extra term by a 256-thread workgroup, a thread's share in ascending
-// order, the shares folded by one tree; every thread receives the result.  scratch [256].
-__device__ __forceinline__ float fm_block_reduce(float val, float *scratch, bool is_max) {
-    const int t = threadIdx.x;
-    scratch[t] = val;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (t < st) scratch[t] = is_max ? fmaxf(scratch[t], scratch[t + st]) : scratch[t] + scratch[t + st];
-        __syncthreads();
-    }
-    const float r = scratch[0];
-    __syncthreads();
-    return r;
-}
-
+// order, the shares folded by block_fold's tree (ndp_device.h); every thread receives the result.  scratch [256].
 __device__ __forceinline__ float fm_block_lse(const float *x, int n, float extra, float *scratch) {
     const int t = threadIdx.x;
     float mm = t == 0 ? extra : -INFINITY;
     for (int i = t; i < n; i += 256) mm = fmaxf(mm, x[i]);
-    const float M = fm_block_reduce(mm, scratch, true);
+    const float M = block_fold_one(mm, scratch, FoldMax());
     float ss = t == 0 ? expf(extra - M) : 0.f;
     for (int i = t; i < n; i += 256) ss += expf(x[i] - M);
-    return M + logf(fm_block_reduce(ss, scratch, false));
+    return M + logf(block_fold_one(ss, scratch, FoldSum()));
 }
 
 extern "C" __global__ void __launch_bounds__(256) k_feat_neg(float *x, int n) {
@@ -276,21 +264,10 @@ struct FmShape {
 };
 
 static int fm_check(const char *who, const int *offA_host, const int *offB_host, int B, int C, FmShape *sh) {
-    static thread_local char msg[160];
-    if (B < 1 || B > 65535) { snprintf(msg, sizeof msg, "%s: B must lie in 1..65535", who); return fail(NDP_E_INVALID, msg); }
-    if (!offA_host || !offB_host) { snprintf(msg, sizeof msg, "%s: null pointer", who); return fail(NDP_E_INVALID, msg); }
-    if (C < 1 || C > FM_MAX_C) { snprintf(msg, sizeof msg, "%s: C must lie in 1..%d", who, FM_MAX_C); return fail(NDP_E_INVALID, msg); }
-    sh->maxA = sh->maxB = 0;
-    for (int side = 0; side < 2; ++side) {
-        const int *off = side ? offB_host : offA_host;
-        int &mx = side ? sh->maxB : sh->maxA;
-        if (off[0] < 0) { snprintf(msg, sizeof msg, "%s: offsets must start at 0 or above", who); return fail(NDP_E_INVALID, msg); }
-        for (int b = 0; b < B; ++b) {
-            if (off[b + 1] < off[b]) { snprintf(msg, sizeof msg, "%s: offsets must be monotone", who); return fail(NDP_E_INVALID, msg); }
-            if (off[b + 1] == off[b]) { snprintf(msg, sizeof msg, "%s: an empty side (every problem needs S >= 1 and T >= 1)", who); return fail(NDP_E_INVALID, msg); }
-            mx = std::max(mx, off[b + 1] - off[b]);
-        }
-    }
+    if (int rc = check_batch(who, offA_host && offB_host ? offA_host : nullptr, B)) return rc;      // B, both pointers, C, then the contents
+    if (C < 1 || C > FM_MAX_C) return failf(NDP_E_INVALID, "%s: C must lie in 1..%d", who, FM_MAX_C);
+    if (int rc = check_offsets(who, offA_host, B, 1, "a non-empty side, S and T", &sh->maxA)) return rc;
+    if (int rc = check_offsets(who, offB_host, B, 1, "a non-empty side, S and T", &sh->maxB)) return rc;
     sh->nA = offA_host[B]; sh->nB = offB_host[B];
     return 0;
 }
@@ -322,7 +299,7 @@ extern "C" int ndp_feat_rowstats(const float *A, const float *Bm, const int *off
 
 // words (4 bytes): per source row f0, f1, arg; per target row g0, g1, arg; per problem ubin, vbin, eu, ev
 extern "C" int ndp_feat_match_workspace(int B, long long nS, long long nT, long long *nbytes) {
-    if (B < 1 || B > 65535 || nS < 1 || nT < 1 || nS > 0x7fffffffLL || nT > 0x7fffffffLL || !nbytes)
+    if (B < 1 || B > NDP_MAX_B || nS < 1 || nT < 1 || nS > 0x7fffffffLL || nT > 0x7fffffffLL || !nbytes)
         return fail(NDP_E_INVALID, "ndp_feat_match_workspace: B in 1..65535, 1 <= nS, nT < 2^31, nbytes not NULL");
     *nbytes = 4 * (3 * (nS + nT) + 4 * (long long)B);
     return 0;

@@ -231,13 +231,8 @@ k_nrf_reg_mean(const double *regp, int n, float *reg) {                        /
     __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += regp[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) reg[0] = (float)(red[0] / (double)n);
+    s = block_fold_one(s, red, FoldSum());
+    if (threadIdx.x == 0) reg[0] = (float)(s / (double)n);
 }
 
 // ---- backward of the head stage per point: dO[p][i] = <g, d warp / d o_i>  (six forward-mode passes; zero rows beyond n) ----

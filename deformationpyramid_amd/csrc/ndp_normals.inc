@@ -124,9 +124,8 @@ k_knn(const float *q, int nq, const float *r, int nr, int K, float *d2, int *idx
 __device__ __forceinline__ void pca_rotate(double &app, double &aqq, double &apq, double &arp, double &arq,
                                            double &v0p, double &v0q, double &v1p, double &v1q, double &v2p, double &v2q) {
     if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);             // (an overflow to inf gives t = 0: no rotation, as it should)
-    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+    double c, s;
+    const double tt = jacobi_cs((aqq - app) / (2.0 * apq), c, s);
     app -= tt * apq;
     aqq += tt * apq;
     apq = 0.0;
@@ -234,6 +233,9 @@ __device__ __forceinline__ float p2p_cos_term(const float *a, const float *b) { 
     return 1.f - fabsf(dot / (fmaxf(la, 1e-6f) * fmaxf(lb, 1e-6f)));
 }
 
+// block_fold's tree (ndp_device.h), kept here in its own words for k_point_to_plane alone: through the template the compiler schedules
+// the last level of this kernel's folds differently, which moves the scan loop below by 48 bytes, and the kernel measured 7 - 9 %
+// slower (profiles/operator_refactor_ab.txt).  With this copy the kernel is instruction for instruction what it was.
 __device__ __forceinline__ double block_sum_256_f64(double v, double *scratch) {
     const int t = threadIdx.x;
     scratch[t] = v;

@@ -224,7 +224,7 @@ __device__ __forceinline__ float l1_sum(const float *d2, int n, float trunc, flo
         const float v = d2[i];
         s += (v >= trunc) ? 0.f : sqrtf(v);
     }
-    return block_sum_256(s, scratch);
+    return block_fold_one(s, scratch, FoldSum());
 }
 __device__ __forceinline__ float sq_sum(const float *x, const float *tt, int K, float *scratch) {
     float s = 0.f;
@@ -232,7 +232,7 @@ __device__ __forceinline__ float sq_sum(const float *x, const float *tt, int K, 
         const float e0 = x[3 * k] - tt[3 * k], e1 = x[3 * k + 1] - tt[3 * k + 1], e2 = x[3 * k + 2] - tt[3 * k + 2];
         s += fmaf(e2, e2, fmaf(e1, e1, e0 * e0));
     }
-    return block_sum_256(s, scratch);
+    return block_fold_one(s, scratch, FoldSum());
 }
 
 extern "C" __global__ void __launch_bounds__(256)

@@ -1,8 +1,8 @@
 // ndp_rigid.inc -- rigid alignment from correspondences: weighted Procrustes (k_rigid_fit), residual counts of given transforms
 // (k_rigid_score), and RANSAC over caller-drawn triples (k_rigid_hyp + k_rigid_score + k_ransac_finish), with ndp_rigid_fit /
 // ndp_rigid_score / ndp_ransac_rigid_workspace / ndp_ransac_rigid.  DESIGN.md "Rigid alignment".  No atomics, no random numbers:
-// every output element has one writer and every sum one fixed order.  All entries are batched: problem b owns the rows
-// off[b] .. off[b + 1] of src / tgt.
+// every output element has one writer and every sum one fixed order (block_fold, ndp_device.h).  All entries are batched: problem b
+// owns the rows off[b] .. off[b + 1] of src / tgt; the entries check the host's copy of off with check_offsets (ndp_abi_common.inc).
 // ------------------------------------------------------------------------------------------------
 // The 3 x 3 decomposition: one-sided (Hestenes) Jacobi in double on one lane.  The columns of A = S V are rotated in pairs until they
 // are orthogonal; then A = U Sigma, the column norms are the singular values (to RELATIVE accuracy: S^T S is never formed) and
@@ -28,10 +28,8 @@ __device__ __forceinline__ bool svd_rotate(double &a0p, double &a1p, double &a2p
     const double alpha = a0p * a0p + a1p * a1p + a2p * a2p, beta = a0q * a0q + a1q * a1q + a2q * a2q;
     const double gamma = a0p * a0q + a1p * a1q + a2p * a2q;
     if (gamma == 0.0 || gamma * gamma <= 1e-34 * (alpha * beta)) return false;      // orthogonal to double already
-    const double zeta = (beta - alpha) / (2.0 * gamma);          // (an overflow to inf gives tt = 0: no rotation, as it should)
-    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-    double x, y;
+    double c, s, x, y;
+    jacobi_cs((beta - alpha) / (2.0 * gamma), c, s);
     x = c * a0p - s * a0q; y = s * a0p + c * a0q; a0p = x; a0q = y;
     x = c * a1p - s * a1q; y = s * a1p + c * a1q; a1p = x; a1q = y;
     x = c * a2p - s * a2q; y = s * a2p + c * a2q; a2p = x; a2q = y;
@@ -103,28 +101,9 @@ __device__ __forceinline__ float rigid_d2(const float (&T)[12], float sx, float 
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
-// NV sums of a 256-thread workgroup in one fixed tree; scratch [NV][256] doubles.  Every thread receives the totals.
-template <int NV>
-__device__ __forceinline__ void block_sum_256_f64v(double (&v)[NV], double *scratch) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) scratch[i * 256 + t] = v[i];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) scratch[i * 256 + t] = scratch[i * 256 + t] + scratch[i * 256 + t + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = scratch[i * 256];
-    __syncthreads();
-}
-
 // Weighted Procrustes of the rows [k0, k1) by one 256-thread workgroup, the reference's arithmetic (procrustes.py:30-43) in double:
 // wn = w / (sum |w| + eps), the two weighted means, Sxy from differences against them -- three passes, a thread's share of each sum
-// in ascending row order, the shares folded by block_sum_256_f64v's tree: nothing depends on which lane runs when.  w NULL: mask
+// in ascending row order, the shares folded by block_fold's tree: nothing depends on which lane runs when.  w NULL: mask
 // (non-zero = 1) or, with both NULL, all ones.  Thread 0 solves; res [13] (LDS) = R, t, condition and *st (LDS) the status reach
 // every thread behind the closing barrier.
 __device__ __forceinline__ void rigid_fit_block(const float *src, const float *tgt, const float *w, const unsigned char *mask, int k0, int k1,
@@ -135,7 +114,7 @@ __device__ __forceinline__ void rigid_fit_block(const float *src, const float *t
         const double wk = w ? (double)w[k] : mask ? (mask[k] ? 1.0 : 0.0) : 1.0;
         a[0] += fabs(wk); a[1] += wk != 0.0 ? 1.0 : 0.0;
     }
-    block_sum_256_f64v<2>(a, scratch);
+    block_fold<2>(a, scratch, FoldSum());
     if (!(a[1] >= 3.0) || !(a[0] > 0.0)) {                       // (uniform: every thread holds the same totals)
         if (t == 0) {
             for (int i = 0; i < 12; ++i) res[i] = (i == 0 || i == 4 || i == 8) ? 1.f : 0.f;
@@ -152,7 +131,7 @@ __device__ __forceinline__ void rigid_fit_block(const float *src, const float *t
         m[0] += wn * (double)sp[0]; m[1] += wn * (double)sp[1]; m[2] += wn * (double)sp[2];
         m[3] += wn * (double)yp[0]; m[4] += wn * (double)yp[1]; m[5] += wn * (double)yp[2];
     }
-    block_sum_256_f64v<6>(m, scratch);
+    block_fold<6>(m, scratch, FoldSum());
     double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = k0 + t; k < k1; k += 256) {
         const double wn = (w ? (double)w[k] : mask ? (mask[k] ? 1.0 : 0.0) : 1.0) * inv;
@@ -163,7 +142,7 @@ __device__ __forceinline__ void rigid_fit_block(const float *src, const float *t
         s[3] += y1 * x0; s[4] += y1 * x1; s[5] += y1 * x2;
         s[6] += y2 * x0; s[7] += y2 * x1; s[8] += y2 * x2;
     }
-    block_sum_256_f64v<9>(s, scratch);
+    block_fold<9>(s, scratch, FoldSum());
     if (t == 0) *st = rigid_solve(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], m[0], m[1], m[2], m[3], m[4], m[5], false, res);
     __syncthreads();
 }
@@ -302,6 +281,8 @@ k_rigid_score(const float *T, const int *flags, const float *src, const float *t
         if (sse) sse[e] = sum;
     }
     if (!partial) return;
+    // FoldBestCount's tree (ndp_device.h) in this kernel's own words: through block_fold the compiler schedules the scoring loop above
+    // differently, and rigid_score measured 1 % slower at K = 5000 in three calls out of three (profiles/operator_refactor_ab.txt).
     int *pc = reinterpret_cast<int *>(sm), *pi = pc + RIGID_HPB;
     __syncthreads();                                             // (the last tile is no longer read)
     pc[t] = h < H ? cnt : -1;
@@ -342,15 +323,8 @@ k_ransac_finish(const float *src, const float *tgt, const int *off, const float 
         const int c = partial[2 * ((size_t)b * n_part + i)], j = partial[2 * ((size_t)b * n_part + i) + 1];
         if (c > bc || (c == bc && j < bi)) { bc = c; bi = j; }
     }
-    int *pc = reinterpret_cast<int *>(scratch), *pi = pc + 256;
-    pc[t] = bc; pi[t] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s && (pc[t + s] > pc[t] || (pc[t + s] == pc[t] && pi[t + s] < pi[t]))) { pc[t] = pc[t + s]; pi[t] = pi[t + s]; }
-        __syncthreads();
-    }
-    bc = pc[0]; bi = pi[0];
-    __syncthreads();
+    const CountIdx best = block_fold_one(CountIdx{bc, bi}, reinterpret_cast<CountIdx *>(scratch), FoldBestCount());
+    bc = best.count; bi = best.idx;
     if (bc <= 0) {
         for (int k = k0 + t; k < k1; k += 256) o.mask[k] = 0;
         if (t < 9) o.R[9 * (size_t)b + t] = (t == 0 || t == 4 || t == 8) ? 1.f : 0.f;
@@ -371,7 +345,7 @@ k_ransac_finish(const float *src, const float *tgt, const int *off, const float 
             o.mask[k] = in ? 1 : 0;
             if (in) { a[0] += 1.0; a[1] += (double)d2; }
         }
-        block_sum_256_f64v<2>(a, scratch);                      // (its barriers also publish the mask to the workgroup)
+        block_fold<2>(a, scratch, FoldSum());                      // (its barriers also publish the mask to the workgroup)
         if (left == 0 || a[0] < 3.0) break;                     // uniform; the mask and the sums are those of Tl
         rigid_fit_block(src, tgt, nullptr, o.mask, k0, k1, (double)eps, scratch, res, &st);
         const int fit_st = st;
@@ -396,27 +370,9 @@ k_ransac_finish(const float *src, const float *tgt, const int *off, const float 
 // ------------------------------------------------------------------------------------------------
 // host entries
 // ------------------------------------------------------------------------------------------------
-#define RIGID_MAX_B 65535
-
-// off_host [B + 1]: the host's copy of `off`, for the checks; min_k: the smallest problem accepted
-static int rigid_check_off(const char *who, const int *off_host, int B, int min_k) {
-    static thread_local char msg[160];
-    if (B < 1 || B > RIGID_MAX_B) { snprintf(msg, sizeof msg, "%s: B must lie in 1..65535", who); return fail(NDP_E_INVALID, msg); }
-    if (!off_host) { snprintf(msg, sizeof msg, "%s: null pointer", who); return fail(NDP_E_INVALID, msg); }
-    if (off_host[0] < 0) { snprintf(msg, sizeof msg, "%s: off must start at 0 or above", who); return fail(NDP_E_INVALID, msg); }
-    for (int b = 0; b < B; ++b) {
-        if (off_host[b + 1] < off_host[b]) { snprintf(msg, sizeof msg, "%s: off must be monotone", who); return fail(NDP_E_INVALID, msg); }
-        if (off_host[b + 1] - off_host[b] < min_k) {
-            snprintf(msg, sizeof msg, "%s: every problem needs K >= %d correspondences", who, min_k);
-            return fail(NDP_E_INVALID, msg);
-        }
-    }
-    return 0;
-}
-
 extern "C" int ndp_rigid_fit(const float *src, const float *tgt, const float *w, const unsigned char *mask, const int *off,
                              const int *off_host, int B, float eps, float *R, float *t, float *condition, int *status, void *stream) {
-    if (int rc = rigid_check_off("ndp_rigid_fit", off_host, B, 0)) return rc;
+    if (int rc = check_offsets("ndp_rigid_fit", off_host, B, 0, "K", nullptr)) return rc;
     if (!src || !tgt || !off || !R || !t || !condition || !status) return fail(NDP_E_INVALID, "ndp_rigid_fit: null pointer");
     if (w && mask) return fail(NDP_E_INVALID, "ndp_rigid_fit: weights or a mask, not both");
     if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(NDP_E_INVALID, "ndp_rigid_fit: eps must be finite and >= 0");
@@ -427,7 +383,7 @@ extern "C" int ndp_rigid_fit(const float *src, const float *tgt, const float *w,
 
 extern "C" int ndp_rigid_score(const float *T, const float *src, const float *tgt, const int *off, const int *off_host, int B, int H,
                                float thr, int *count, float *sse, void *stream) {
-    if (int rc = rigid_check_off("ndp_rigid_score", off_host, B, 1)) return rc;
+    if (int rc = check_offsets("ndp_rigid_score", off_host, B, 1, "K", nullptr)) return rc;
     if (H < 1) return fail(NDP_E_INVALID, "ndp_rigid_score: H >= 1");
     if (!(thr > 0.f) || !std::isfinite(thr)) return fail(NDP_E_INVALID, "ndp_rigid_score: thr must be positive and finite");
     if (!T || !src || !tgt || !off || !count) return fail(NDP_E_INVALID, "ndp_rigid_score: null pointer");
@@ -439,7 +395,7 @@ extern "C" int ndp_rigid_score(const float *T, const float *src, const float *tg
 }
 
 extern "C" int ndp_ransac_rigid_workspace(int B, int H, long long *nbytes) {
-    if (B < 1 || B > RIGID_MAX_B || H < 1 || !nbytes) return fail(NDP_E_INVALID, "ndp_ransac_rigid_workspace: B in 1..65535, H >= 1, nbytes not NULL");
+    if (B < 1 || B > NDP_MAX_B || H < 1 || !nbytes) return fail(NDP_E_INVALID, "ndp_ransac_rigid_workspace: B in 1..65535, H >= 1, nbytes not NULL");
     const long long bh = (long long)B * H, parts = (long long)B * ((H + RIGID_HPB - 1) / RIGID_HPB);
     *nbytes = 4 * (12 * bh + bh + bh + 2 * parts);
     return 0;
@@ -448,7 +404,7 @@ extern "C" int ndp_ransac_rigid_workspace(int B, int H, long long *nbytes) {
 extern "C" int ndp_ransac_rigid(const float *src, const float *tgt, const int *off, const int *off_host, int B, const int *triples, int H,
                                 float thr, float edge_ratio, int refine_iters, void *ws, float *R, float *t, unsigned char *mask, int *count,
                                 float *rmse, int *best, int *status, int *h_count, int *h_flags, float *h_T, void *stream) {
-    if (int rc = rigid_check_off("ndp_ransac_rigid", off_host, B, 3)) return rc;
+    if (int rc = check_offsets("ndp_ransac_rigid", off_host, B, 3, "K", nullptr)) return rc;
     if (H < 1) return fail(NDP_E_INVALID, "ndp_ransac_rigid: H >= 1");
     if (!(thr > 0.f) || !std::isfinite(thr)) return fail(NDP_E_INVALID, "ndp_ransac_rigid: thr must be positive and finite");
     if (!(edge_ratio >= 0.f) || !(edge_ratio <= 1.f)) return fail(NDP_E_INVALID, "ndp_ransac_rigid: edge_ratio must lie in 0..1 (0: no edge check)");

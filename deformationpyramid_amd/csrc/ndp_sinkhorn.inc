@@ -190,17 +190,11 @@ k_sinkhorn_final(SkFinal p) {
 // loss = scale (sum_x / n + sum_y / m) over the per-workgroup partials, each side folded in one fixed order
 extern "C" __global__ void __launch_bounds__(256)
 k_sinkhorn_loss(const double *partials, int nb, int n, int m, double scale, float *loss) {
-    __shared__ double s[2][256];
-    const int t = threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int i = t; i < nb; i += 256) { a += partials[i]; b += partials[(size_t)nb + i]; }
-    s[0][t] = a; s[1][t] = b;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h) { s[0][t] += s[0][t + h]; s[1][t] += s[1][t + h]; }
-        __syncthreads();
-    }
-    if (t == 0) *loss = (float)(scale * (s[0][0] / n + s[1][0] / m));
+    __shared__ double scratch[2 * 256];
+    double s[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < nb; i += 256) { s[0] += partials[i]; s[1] += partials[(size_t)nb + i]; }
+    block_fold<2>(s, scratch, FoldSum());
+    if (threadIdx.x == 0) *loss = (float)(scale * (s[0] / n + s[1] / m));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -35,6 +35,37 @@ def cap(n):
     return max(TILE, (n + TILE - 1) // TILE * TILE)
 
 
+def _workspace(entry, dims, dev, dtype=torch.float32, per=1):
+    """Ask the library's size query `entry`(*dims, &size) and allocate that workspace on dev: a tensor of `dtype`, one element of
+    which holds `per` of the query's units (floats or bytes; the count is rounded up).  Every entry accepts a workspace at least as
+    large as its query asked for, so a caller that must name the size passes the tensor's own (4 * ws.numel() bytes: the KPConv
+    queries answer in multiples of 16 bytes, so that is their figure)."""
+    size = ctypes.c_longlong()
+    N.check(getattr(N.lib(), entry)(*dims, ctypes.byref(size)), entry)
+    return torch.empty((size.value + per - 1) // per, device=dev, dtype=dtype)
+
+
+def _nn_result(S, T, dev):
+    """The tensors of a nearest-neighbour result, unfilled: (d2x [S], ix [S] int32, d2y [T], iy [T] int32)."""
+    return (torch.empty(S, device=dev), torch.empty(S, device=dev, dtype=torch.int32),
+            torch.empty(T, device=dev), torch.empty(T, device=dev, dtype=torch.int32))
+
+
+def _check_prev_idx(prev_idx_x, S, prev_idx_y, T):
+    for p, n, name in ((prev_idx_x, S, "prev_idx_x"), (prev_idx_y, T, "prev_idx_y")):
+        if p is not None and (p.dtype != torch.int32 or not p.is_cuda or not p.is_contiguous() or p.numel() != n):
+            raise ValueError(f"{name} must be a contiguous int32 device tensor with one entry per query")
+
+
+def _host_offsets(n, offsets, name, dev):
+    """offsets over n rows (None: one problem; else B + 1 ascending ints, host side) -> (device int32 tensor, ctypes host copy).  The
+    entries check the host copy; the kernels read the device one."""
+    off = [0, n] if offsets is None else [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+    if len(off) < 2 or off[0] != 0 or off[-1] != n:
+        raise ValueError(f"{name} must run from 0 to {n} in B + 1 entries, got {off[:4]}{'...' if len(off) > 4 else ''}")
+    return torch.tensor(off, dtype=torch.int32).to(dev), (ctypes.c_int * len(off))(*off)
+
+
 def level_fwd(desc: LayerDesc, params, level, k0, x, save=False, want_nonrig=False):
     """x [n,3] -> x_out [n,3]; with save also (act [depth,cap,width], heads [cap,24]; [3,cap,128] for the shipped 128 / 3); with
     want_nonrig the gate values [n] of a level that carries the nonrigidity head are appended.  width / depth other than 128 / 3 run on
@@ -191,8 +222,7 @@ def pair_means(src, tgt, out=None):
 def chamfer_nn(x, y):
     _chk(x, "x"); _chk(y, "y")
     S, T = x.shape[0], y.shape[0]
-    d2x = torch.empty(S, device=x.device); d2y = torch.empty(T, device=x.device)
-    ix = torch.empty(S, device=x.device, dtype=torch.int32); iy = torch.empty(T, device=x.device, dtype=torch.int32)
+    d2x, ix, d2y, iy = _nn_result(S, T, x.device)
     N.check(N.lib().ndp_chamfer_nn_fwd(_p(x), S, _p(y), T, _p(d2x), _p(ix), _p(d2y), _p(iy), N.stream_ptr(x.device)),
             "ndp_chamfer_nn_fwd")
     return d2x, ix, d2y, iy
@@ -203,11 +233,8 @@ def chamfer_nn_onepass(x, y, matrix=False):
     matrix: the variant that forms the distances on the bf16 matrix pipe and re-evaluates the candidates exactly (engine nn_mode 2)."""
     _chk(x, "x"); _chk(y, "y")
     S, T = x.shape[0], y.shape[0]
-    nr = ctypes.c_longlong()
-    N.check(N.lib().ndp_engine_nn_workspace(cap(S), cap(T), ctypes.byref(nr)), "ndp_engine_nn_workspace")
-    ws_row = torch.empty(nr.value, device=x.device)
-    d2x = torch.empty(S, device=x.device); d2y = torch.empty(T, device=x.device)
-    ix = torch.empty(S, device=x.device, dtype=torch.int32); iy = torch.empty(T, device=x.device, dtype=torch.int32)
+    ws_row = _workspace("ndp_engine_nn_workspace", (cap(S), cap(T)), x.device)
+    d2x, ix, d2y, iy = _nn_result(S, T, x.device)
     fn = N.lib().ndp_chamfer_nn_matrix if matrix else N.lib().ndp_chamfer_nn_onepass
     N.check(fn(_p(x), S, _p(y), T, _p(d2x), _p(ix), _p(d2y), _p(iy), _p(ws_row), N.stream_ptr(x.device)),
             "ndp_chamfer_nn_matrix" if matrix else "ndp_chamfer_nn_onepass")
@@ -219,14 +246,9 @@ def chamfer_nn_cells(x, y, prev_idx_x=None, prev_idx_y=None):
     prev_idx_x [S] / prev_idx_y [T] (int32, optional): seed indices, e.g. the previous call's; ANY values give the same result."""
     _chk(x, "x"); _chk(y, "y")
     S, T = x.shape[0], y.shape[0]
-    for p, n, name in ((prev_idx_x, S, "prev_idx_x"), (prev_idx_y, T, "prev_idx_y")):
-        if p is not None and (p.dtype != torch.int32 or not p.is_cuda or not p.is_contiguous() or p.numel() != n):
-            raise ValueError(f"{name} must be a contiguous int32 device tensor with one entry per query")
-    nf = ctypes.c_longlong()
-    N.check(N.lib().ndp_chamfer_nn_cells_workspace(T, ctypes.byref(nf)), "ndp_chamfer_nn_cells_workspace")
-    ws = torch.empty(nf.value, device=x.device)
-    d2x = torch.empty(S, device=x.device); d2y = torch.empty(T, device=x.device)
-    ix = torch.empty(S, device=x.device, dtype=torch.int32); iy = torch.empty(T, device=x.device, dtype=torch.int32)
+    _check_prev_idx(prev_idx_x, S, prev_idx_y, T)
+    ws = _workspace("ndp_chamfer_nn_cells_workspace", (T,), x.device)
+    d2x, ix, d2y, iy = _nn_result(S, T, x.device)
     N.check(N.lib().ndp_chamfer_nn_cells(_p(x), S, _p(y), T, _p(prev_idx_x), _p(prev_idx_y), _p(d2x), _p(ix), _p(d2y), _p(iy), _p(ws),
                                          N.stream_ptr(x.device)), "ndp_chamfer_nn_cells")
     return d2x, ix, d2y, iy
@@ -237,14 +259,9 @@ def chamfer_nn_cells_wide(x, y, prev_idx_x=None, prev_idx_y=None):
     chamfer_nn for ANY prev_idx_x [S] / prev_idx_y [T] (int32, optional)."""
     _chk(x, "x"); _chk(y, "y")
     S, T = x.shape[0], y.shape[0]
-    for p, n, name in ((prev_idx_x, S, "prev_idx_x"), (prev_idx_y, T, "prev_idx_y")):
-        if p is not None and (p.dtype != torch.int32 or not p.is_cuda or not p.is_contiguous() or p.numel() != n):
-            raise ValueError(f"{name} must be a contiguous int32 device tensor with one entry per query")
-    nf = ctypes.c_longlong()
-    N.check(N.lib().ndp_chamfer_nn_cells_wide_workspace(S, T, ctypes.byref(nf)), "ndp_chamfer_nn_cells_wide_workspace")
-    ws = torch.empty(nf.value, device=x.device)
-    d2x = torch.empty(S, device=x.device); d2y = torch.empty(T, device=x.device)
-    ix = torch.empty(S, device=x.device, dtype=torch.int32); iy = torch.empty(T, device=x.device, dtype=torch.int32)
+    _check_prev_idx(prev_idx_x, S, prev_idx_y, T)
+    ws = _workspace("ndp_chamfer_nn_cells_wide_workspace", (S, T), x.device)
+    d2x, ix, d2y, iy = _nn_result(S, T, x.device)
     N.check(N.lib().ndp_chamfer_nn_cells_wide(_p(x), S, _p(y), T, _p(prev_idx_x), _p(prev_idx_y), _p(d2x), _p(ix), _p(d2y), _p(iy), _p(ws),
                                               N.stream_ptr(x.device)), "ndp_chamfer_nn_cells_wide")
     return d2x, ix, d2y, iy
@@ -275,17 +292,13 @@ def sinkhorn_divergence(x, y, blur, reach=None, scaling=0.5, want_grad=True, wan
     geomloss.SamplesLoss("sinkhorn", p=2, blur, reach, scaling) as restated in DESIGN.md; reach None: balanced).
     -> (loss [1], grad_x [n,3] | None, potentials [2n + 2m] = (F_ba, F_aa, G_ab, G_bb) | None).  grad_x is dloss/dx with y and the
     dual potentials held fixed.  One host read: the diameter of the joint bounding box, as the library's `.item()`."""
-    _chk(x, "x"); _chk(y, "y")
-    for t, name in ((x, "x"), (y, "y")):
-        if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-            raise ValueError(f"{name} must be a [N, 3] tensor with N >= 1, got {tuple(t.shape)}")
+    _chk(x, "x"); _chk(y, "y")                                      # both devices before either shape
+    _cloud(x, "x"); _cloud(y, "y")
     n, m = x.shape[0], y.shape[0]
     lo = torch.minimum(x.min(dim=0).values, y.min(dim=0).values).double()
     hi = torch.maximum(x.max(dim=0).values, y.max(dim=0).values).double()
     diameter = float((hi - lo).norm().item())
-    nf = ctypes.c_longlong()
-    N.check(N.lib().ndp_sinkhorn_workspace(n, m, ctypes.byref(nf)), "ndp_sinkhorn_workspace")
-    ws = torch.empty(nf.value // 2 + 1, device=x.device, dtype=torch.float64)       # (float64: 8-byte aligned)
+    ws = _workspace("ndp_sinkhorn_workspace", (n, m), x.device, torch.float64, per=2)      # (in floats; float64: 8-byte aligned)
     loss = torch.empty(1, device=x.device)
     gx = torch.empty_like(x) if want_grad else None
     pot = torch.empty(2 * n + 2 * m, device=x.device) if want_potentials else None
@@ -358,17 +371,12 @@ def point_to_plane(x, y, nx, ny, trunc=math.inf, mode=0, nn=None, want_grad=True
 
 
 def _rigid_problems(src, tgt, offsets):
-    """src, tgt [sum K,3] and offsets (None: one problem; else B + 1 ascending ints, host side) -> (B, device int32 tensor, ctypes
-    host copy).  The entries check the host copy; the kernels read the device one."""
+    """src, tgt [sum K,3] and their row offsets (_host_offsets) -> (B, device offsets, host offsets)."""
     _cloud(src, "src"); _cloud(tgt, "tgt")
     if tgt.shape != src.shape:
         raise ValueError(f"src and tgt must list the same correspondences, got {tuple(src.shape)} and {tuple(tgt.shape)}")
-    n = src.shape[0]
-    off = [0, n] if offsets is None else [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
-    if len(off) < 2 or off[0] != 0 or off[-1] != n:
-        raise ValueError(f"offsets must run from 0 to {n} in B + 1 entries, got {off[:4]}{'...' if len(off) > 4 else ''}")
-    host = (ctypes.c_int * len(off))(*off)
-    return len(off) - 1, torch.tensor(off, dtype=torch.int32).to(src.device), host
+    off, host = _host_offsets(src.shape[0], offsets, "offsets", src.device)
+    return len(host) - 1, off, host
 
 
 def rigid_fit(src, tgt, w=None, mask=None, eps=1e-4, offsets=None):
@@ -425,9 +433,7 @@ def ransac_rigid(src, tgt, triples, thr, edge_ratio=0.9, refine_iters=2, offsets
     if triples.ndim != 3 or triples.shape[0] != B or triples.shape[2] != 3 or triples.shape[1] < 1:
         raise ValueError(f"triples must be [{B}, H, 3] with H >= 1, got {tuple(triples.shape)}")
     H, dev = triples.shape[1], src.device
-    nb = ctypes.c_longlong()
-    N.check(N.lib().ndp_ransac_rigid_workspace(B, H, ctypes.byref(nb)), "ndp_ransac_rigid_workspace")
-    ws = torch.empty(nb.value // 4, device=dev, dtype=torch.int32)
+    ws = _workspace("ndp_ransac_rigid_workspace", (B, H), dev, torch.int32, per=4)
     out = dict(R=torch.empty(B, 3, 3, device=dev), t=torch.empty(B, 3, device=dev), mask=torch.empty(src.shape[0], device=dev, dtype=torch.uint8),
                count=torch.empty(B, device=dev, dtype=torch.int32), rmse=torch.empty(B, device=dev),
                best=torch.empty(B, device=dev, dtype=torch.int32), status=torch.empty(B, device=dev, dtype=torch.int32))
@@ -446,13 +452,6 @@ def ransac_rigid(src, tgt, triples, thr, edge_ratio=0.9, refine_iters=2, offsets
 FEAT_MODES = {"dual_softmax": 0, "sinkhorn": 1, "mutual_nn": 2}
 
 
-def _feat_offsets(n, offsets, name, dev):
-    off = [0, n] if offsets is None else [int(v) for v in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
-    if len(off) < 2 or off[0] != 0 or off[-1] != n:
-        raise ValueError(f"{name} must run from 0 to {n} in B + 1 entries, got {off[:4]}{'...' if len(off) > 4 else ''}")
-    return torch.tensor(off, dtype=torch.int32).to(dev), (ctypes.c_int * len(off))(*off)
-
-
 def _feat_problems(a, b, offsets_a, offsets_b):
     """a [sum S,C], b [sum T,C] and their B + 1 host-side row offsets (None: one problem) -> (B, C, device offsets a / b, host a / b)."""
     if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor) or a.ndim != 2 or b.ndim != 2:
@@ -460,8 +459,8 @@ def _feat_problems(a, b, offsets_a, offsets_b):
     if a.shape[1] != b.shape[1]:
         raise ValueError(f"both sides need the same descriptor length C, got {a.shape[1]} and {b.shape[1]}")
     _chk(a, "a"); _chk(b, "b")
-    oa, ha = _feat_offsets(a.shape[0], offsets_a, "offsets_a", a.device)
-    ob, hb = _feat_offsets(b.shape[0], offsets_b, "offsets_b", a.device)
+    oa, ha = _host_offsets(a.shape[0], offsets_a, "offsets_a", a.device)
+    ob, hb = _host_offsets(b.shape[0], offsets_b, "offsets_b", a.device)
     if len(ha) != len(hb):
         raise ValueError(f"both sides must list the same problems, got {len(ha) - 1} and {len(hb) - 1}")
     return len(ha) - 1, a.shape[1], oa, ob, ha, hb
@@ -497,9 +496,7 @@ def feat_match(fs, ft, mode="dual_softmax", temperature=0.1, bin_score=1.0, iter
         raise ValueError(f"mode must be one of {sorted(FEAT_MODES)}, got {mode!r}")
     B, C, os_, ot, hs, ht = _feat_problems(fs, ft, offsets_s, offsets_t)
     dev = fs.device
-    nb = ctypes.c_longlong()
-    N.check(N.lib().ndp_feat_match_workspace(B, fs.shape[0], ft.shape[0], ctypes.byref(nb)), "ndp_feat_match_workspace")
-    ws = torch.empty(nb.value // 4, device=dev, dtype=torch.int32)
+    ws = _workspace("ndp_feat_match_workspace", (B, fs.shape[0], ft.shape[0]), dev, torch.int32, per=4)
     match_t, conf = torch.empty(fs.shape[0], device=dev, dtype=torch.int32), torch.empty(fs.shape[0], device=dev)
     N.check(N.lib().ndp_feat_match(_p(fs), _p(ft), _p(os_), _p(ot), hs, ht, B, C, FEAT_MODES[mode], float(temperature), float(bin_score),
                                    int(iters), float(thr), int(bool(mutual)), _p(ws), _p(match_t), _p(conf), N.stream_ptr(dev)),
@@ -548,14 +545,12 @@ def voxel_subsample(points, lengths, dl, features=None, max_p=0):
     if features is not None:
         _chk(features, "features")
     B, dev = len(hl), points.device
-    nb = ctypes.c_longlong()
-    N.check(N.lib().ndp_voxel_subsample_workspace(n, B, ctypes.byref(nb)), "ndp_voxel_subsample_workspace")
-    ws = torch.empty((nb.value + 15) // 16 * 4, device=dev, dtype=torch.int32)
+    ws = _workspace("ndp_voxel_subsample_workspace", (n, B), dev, torch.int32, per=4)
     out = torch.empty(n, 3, device=dev)
     out_f = torch.empty(n, F, device=dev) if F else None
     inverse = torch.empty(n, device=dev, dtype=torch.int32)
     out_len = (ctypes.c_int * B)()
-    N.check(N.lib().ndp_voxel_subsample(_p(points), _p(features), F, hl, B, dl, int(max_p), _p(ws), nb.value, _p(out), _p(out_f), _p(inverse),
+    N.check(N.lib().ndp_voxel_subsample(_p(points), _p(features), F, hl, B, dl, int(max_p), _p(ws), 4 * ws.numel(), _p(out), _p(out_f), _p(inverse),
                                         out_len, N.stream_ptr(dev)), "ndp_voxel_subsample")
     m = sum(out_len)
     return out[:m], torch.tensor(list(out_len), dtype=torch.int32), (out_f[:m] if F else None), inverse
@@ -578,13 +573,11 @@ def radius_search(q, s, q_lengths, s_lengths, radius, max_neighbors, want_d2=Fal
         raise ValueError(f"max_neighbors must not exceed {RADIUS_MAX_K}, got {max_neighbors}")
     _chk(q, "q"); _chk(s, "s")
     B, dev = len(hq), q.device
-    nb = ctypes.c_longlong()
-    N.check(N.lib().ndp_radius_search_workspace(nq, ns, B, ctypes.byref(nb)), "ndp_radius_search_workspace")
-    ws = torch.empty((nb.value + 15) // 16 * 4, device=dev, dtype=torch.int32)
+    ws = _workspace("ndp_radius_search_workspace", (nq, ns, B), dev, torch.int32, per=4)
     counts = torch.empty(nq, device=dev, dtype=torch.int32)
 
     def run(K, idx, d2):
-        N.check(N.lib().ndp_radius_search(_p(q), _p(s), hq, hs, B, radius, K, _p(ws), nb.value, _p(idx), _p(d2), _p(counts),
+        N.check(N.lib().ndp_radius_search(_p(q), _p(s), hq, hs, B, radius, K, _p(ws), 4 * ws.numel(), _p(idx), _p(d2), _p(counts),
                                           N.stream_ptr(dev)), "ndp_radius_search")
 
     K = 0 if max_neighbors is None else int(max_neighbors)
@@ -685,22 +678,30 @@ def level_warp(layer, x):
     return out, (nr if layer.desc.nonrigidity else None)
 
 
+def _save_pair_grads(ctx, gx, gy, dev):
+    """What the two pair losses keep for their backward: dloss/dx and dloss/dy as the forward's kernels left them (empty: not asked for)."""
+    none = torch.empty(0, device=dev)
+    ctx.save_for_backward(gx if gx is not None else none, gy if gy is not None else none)
+
+
+def _pair_grads(ctx, g, n_inputs):
+    """... and their backward: the saved gradients scaled by g for x and y, None for the other inputs."""
+    gx, gy = ctx.saved_tensors
+    return ((gx * g if gx.numel() else None), (gy * g if gy.numel() else None)) + (None,) * (n_inputs - 2)
+
+
 class _ChamferFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, trunc, point_sum=False):
         xd, yd = x.detach().contiguous(), y.detach().contiguous()
         res = chamfer_l1(xd, yd, trunc, want_grad=x.requires_grad, point_sum=point_sum, want_grad_y=y.requires_grad)
-        loss, gx = res[0], res[1]
-        gy = res[3] if y.requires_grad else None
-        none = torch.empty(0, device=x.device)
-        ctx.save_for_backward(gx if gx is not None else none, gy if gy is not None else none)
-        return loss[0]
+        _save_pair_grads(ctx, res[1], res[3] if y.requires_grad else None, x.device)
+        return res[0][0]
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        gx, gy = ctx.saved_tensors
-        return (gx * g if gx.numel() else None), (gy * g if gy.numel() else None), None, None
+        return _pair_grads(ctx, g, 4)
 
 
 def chamfer_distance(x, y, trunc, point_sum=False):
@@ -714,10 +715,8 @@ class _PointToPlaneFn(torch.autograd.Function):
         xd, yd = x.detach().contiguous(), y.detach().contiguous()
         res = point_to_plane(xd, yd, nx.detach().contiguous(), ny.detach().contiguous(), trunc, mode,
                              want_grad=x.requires_grad, want_grad_y=y.requires_grad)
-        out, gx = res[0], res[1]
-        gy = res[3] if y.requires_grad else None
-        none = torch.empty(0, device=x.device)
-        ctx.save_for_backward(gx if gx is not None else none, gy if gy is not None else none)
+        out = res[0]
+        _save_pair_grads(ctx, res[1], res[3] if y.requires_grad else None, x.device)
         parts = out[1:].clone()
         ctx.mark_non_differentiable(parts, res[2][1])
         return out[0], parts, res[2][1]
@@ -725,8 +724,7 @@ class _PointToPlaneFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g, g_parts, g_idx):
-        gx, gy = ctx.saved_tensors
-        return (gx * g if gx.numel() else None), (gy * g if gy.numel() else None), None, None, None, None
+        return _pair_grads(ctx, g, 6)
 
 
 def point_to_plane_distance(x, y, nx, ny, trunc=math.inf, mode=0):

@@ -250,6 +250,8 @@ _SIGS = {
     "ndp_voxel_subsample": [V, V, I, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, c_int_p, V],
     "ndp_radius_search_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_radius_search": [V, V, c_int_p, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, V],
+    "ndp_kpconv_forward_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_kpconv_forward": [V, V, V, V, V, V, ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, F, I, I, I, V, ctypes.c_longlong, V, V],
 }
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

@@ -42,3 +42,4 @@
 #include "ndp_rigid.inc"               // rigid alignment from correspondences: weighted Procrustes, residual counts, RANSAC over given triples
 #include "ndp_match.inc"               // descriptor matching: S x T row statistics on the f32 MFMA, dual-softmax / dustbin OT / mutual-NN
 #include "ndp_kpconv.inc"              // KPConv inputs: voxel barycentre subsampling and fixed-radius neighbours on a sorted cell-key table
+#include "ndp_kpconv_conv.inc"         // KPConv convolution: neighbour aggregation and the contraction with the kernel weights on the f32 MFMA, one launch

@@ -596,6 +596,56 @@ def radius_search(q, s, q_lengths, s_lengths, radius, max_neighbors, want_d2=Fal
     return (idx, counts, d2) if want_d2 else (idx, counts)
 
 
+KPCONV_INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
+KPCONV_AGGREGATION = {"sum": 0, "closest": 1}
+KPCONV_MAX_K, KPCONV_MAX_C = 32, 1024
+
+
+def kpconv(q, s, idx, x, weights, kernel_points, extent, influence="linear", aggregation="sum", normalize=True):
+    """Rigid KPConv forward (csrc/ndp_kpconv_conv.inc: k_kpc_forward, both products on the f32-input MFMA) -> y [Nq, Cout].
+    q [Nq,3] queries, s [Ns,3] supports, idx [Nq,H] int32 or int64 stacked support rows (radius_search's; every value outside
+    0 .. Ns-1 is a shadow and contributes nothing), x [Ns,Cin] features (made contiguous if they are not), weights [K,Cin,Cout],
+    kernel_points [K,3].  y[n] = sum_k sum_c (sum_h w(n,h,k) x[idx[n,h],c]) W[k,c,:] with the kernel-point influence w of the
+    squared distance between s[idx[n,h]] - q[n] and kernel_points[k]: "constant" 1, "linear" max(0, 1 - d / extent), "gaussian"
+    exp(-d^2 / (2 (0.3 extent)^2 + 1e-9)); aggregation "closest" keeps, per neighbour, only its nearest kernel point; normalize
+    divides by max(1, number of neighbours whose feature row sums to a positive number), the reference's term.  K <= 32, H <= 64,
+    Cin, Cout <= 1024.  Forward only; does not synchronise."""
+    _stacked(q, "q"); _stacked(s, "s")
+    nq, ns, extent = q.shape[0], s.shape[0], float(extent)
+    if not isinstance(idx, torch.Tensor) or idx.ndim != 2 or idx.shape[0] != nq or idx.shape[1] < 1 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"idx must be an int32 or int64 tensor [Nq, H] with Nq = {nq} and H >= 1, got {getattr(idx, 'shape', type(idx))} "
+                         f"{getattr(idx, 'dtype', '')}")
+    if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[0] != ns or x.shape[1] < 1:
+        raise ValueError(f"x must be [Ns, Cin] with Ns = {ns} and Cin >= 1, got {getattr(x, 'shape', type(x))}")
+    cin = x.shape[1]
+    if not isinstance(weights, torch.Tensor) or weights.ndim != 3 or weights.shape[1] != cin or weights.shape[0] < 1 or weights.shape[2] < 1:
+        raise ValueError(f"weights must be [K, Cin, Cout] with Cin = {cin}, got {getattr(weights, 'shape', type(weights))}")
+    K, cout, H = weights.shape[0], weights.shape[2], idx.shape[1]
+    if not isinstance(kernel_points, torch.Tensor) or tuple(kernel_points.shape) != (K, 3):
+        raise ValueError(f"kernel_points must be [K, 3] with K = {K}, got {getattr(kernel_points, 'shape', type(kernel_points))}")
+    if influence not in KPCONV_INFLUENCE:
+        raise ValueError(f"influence must be one of {sorted(KPCONV_INFLUENCE)}, got {influence!r}")
+    if aggregation not in KPCONV_AGGREGATION:
+        raise ValueError(f"aggregation must be one of {sorted(KPCONV_AGGREGATION)}, got {aggregation!r}")
+    if not (extent > 0 and math.isfinite(extent)):
+        raise ValueError(f"extent must be positive and finite, got {extent}")
+    if H > RADIUS_MAX_K or K > KPCONV_MAX_K or cin > KPCONV_MAX_C or cout > KPCONV_MAX_C:
+        raise ValueError(f"served are H <= {RADIUS_MAX_K}, K <= {KPCONV_MAX_K}, Cin, Cout <= {KPCONV_MAX_C}; got H = {H}, K = {K}, "
+                         f"Cin = {cin}, Cout = {cout}")
+    _chk(q, "q"); _chk(s, "s")
+    if idx.dtype == torch.int64:                                   # the reference's tables; a value beyond int32 is a shadow either way
+        idx = idx.clamp(-1, ns).to(torch.int32)
+    idx, x = idx.contiguous(), x.contiguous()
+    _chk(idx, "idx", torch.int32); _chk(x, "x"); _chk(weights.detach(), "weights"); _chk(kernel_points.detach(), "kernel_points")
+    dev = q.device
+    ws = _workspace("ndp_kpconv_forward_workspace", (nq, ns, H, K, cin, cout), dev, torch.int32, per=4)
+    y = torch.empty(nq, cout, device=dev)
+    N.check(N.lib().ndp_kpconv_forward(_p(q), _p(s), _p(idx), _p(x), _p(weights), _p(kernel_points), nq, ns, H, K, cin, cout, extent,
+                                       KPCONV_INFLUENCE[influence], KPCONV_AGGREGATION[aggregation], int(bool(normalize)), _p(ws),
+                                       4 * ws.numel(), _p(y), N.stream_ptr(dev)), "ndp_kpconv_forward")
+    return y
+
+
 def landmark_mse(x, t):
     _chk(x, "x"); _chk(t, "t")
     loss = torch.empty(1, device=x.device)

@@ -409,6 +409,30 @@ int ndp_radius_search_workspace(long long nq, long long ns, int B, long long *nb
 int ndp_radius_search(const float *q, const float *s, const int *q_lengths_host, const int *s_lengths_host, int B, float radius, int K,
                       void *ws, long long ws_bytes, int *idx, float *d2, int *counts, void *stream);
 
+/* KPConv convolution (csrc/ndp_kpconv_conv.inc; DESIGN.md "KPConv convolution"), ABI 214: the forward of the reference's rigid
+ * KPConv (lepard/blocks.py:229-374 with deformable = False) in one launch, plus a pre-pass over x when normalize = 1.
+ * q [nq][3] queries, s [ns][3] supports, idx [nq][H] int32 stacked-global support rows as ndp_radius_search writes them,
+ * x [ns][cin] features, W [K][cin][cout] weights, kp [K][3] kernel points, y [nq][cout]; all contiguous, on the device.
+ *   valid(n,h) = 0 <= idx[n,h] < ns.  EVERY other value (the shadow ns, a negative, anything larger) is a shadow: nothing is read
+ *                for it and it contributes nothing in any mode.  The reference would raise; here a bad table cannot fault.
+ *   d2(n,h,k)  = |(s[idx[n,h]] - q[n]) - kp[k]|^2 in fp32
+ *   w(n,h,k)   = 1 (influence 0, constant) | max(0, 1 - sqrt(d2) / extent) (1, linear) | exp(-d2 / (2 (0.3 extent)^2 + 1e-9)) (2, gaussian)
+ *   aggregation 1 (closest): w is kept only for the k with the smallest d2(n,h,.), the lowest k among equals; 0 (sum): for all k
+ *   wf[n,k,c]  = sum_h w(n,h,k) x[idx[n,h],c]        y[n,o] = sum_k sum_c wf[n,k,c] W[k,c,o]
+ *   normalize 1: y[n,:] /= max(1, #{h valid : sum_c x[idx[n,h],c] > 0}), the reference's term (blocks.py:368-372), an IEEE fp32
+ *                division; the flag of a support row is computed once per call in a fixed order.  normalize 0: the plain sum.
+ * Both products run on the f32-input MFMA (exact fp32 products, one rounding per term, a fixed order); there are no atomics, the
+ * same inputs give the same bits, and a query's result does not depend on the other queries of the call.  Nothing is
+ * data-dependent: ndp_kpconv_forward launches on `stream` and DOES NOT synchronise.  No backward pass.
+ * ws: at least ndp_kpconv_forward_workspace(...) bytes (the row flags), 16-byte aligned; ws_bytes is checked.  The query needs no device.
+ *   NDP_E_UNSUPPORTED: outside 1 <= K <= 32, 1 <= H <= 64, 1 <= cin, cout <= 1024, 1 <= nq, ns <= 2^30 on the large side.
+ *   NDP_E_INVALID: a dimension < 1, a NULL or misaligned pointer, extent not positive and finite, influence outside 0..2,
+ *   aggregation or normalize outside 0..1, a workspace too small.                                                                 */
+int ndp_kpconv_forward_workspace(long long nq, long long ns, int H, int K, int cin, int cout, long long *nbytes);
+int ndp_kpconv_forward(const float *q, const float *s, const int *idx, const float *x, const float *W, const float *kp,
+                       long long nq, long long ns, int H, int K, int cin, int cout, float extent, int influence, int aggregation,
+                       int normalize, void *ws, long long ws_bytes, float *y, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

@@ -252,7 +252,11 @@ _SIGS = {
     "ndp_radius_search": [V, V, c_int_p, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, V],
     "ndp_kpconv_forward_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_kpconv_forward": [V, V, V, V, V, V, ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, F, I, I, I, V, ctypes.c_longlong, V, V],
+    "ndp_attention_forward": [V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, V, V],
+    "ndp_feat_conf_workspace": [I, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_feat_conf": [V, V, V, V, c_int_p, c_int_p, I, I, F, V, V, I, I, V],
 }
+ABI_VERSION = 215                                   # ndp_version() of the library these signatures describe
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 
 

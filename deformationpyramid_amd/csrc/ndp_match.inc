@@ -369,3 +369,123 @@ extern "C" int ndp_feat_match(const float *fs, const float *ft, const int *offS,
     HIP_TRY(hipGetLastError(), "k_feat_match_finish launch");
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The dense dual-softmax confidence matrix (ABI 215), for the callers that need the matrix itself: Lepard's soft-Procrustes layer and
+// its conf_matrix_pred.  conf[b, i, j] = exp(a_ij - lse_row_i) exp(a_ij - lse_col_j), a_ij = <fs_i, ft_j> / (C temperature), into
+// [B, Smax, Tmax]; everything outside a problem's S x T is exactly 0, what the reference's masked soft-maxes give its padding.
+// lse_row / lse_col come from two launches of k_feat_rowstats.  k_feat_conf walks the matrix as k_feat_rowstats does -- the same
+// staging (fm_fetch / fm_stage), the same MFMA chain over ascending k, a_ij = alpha * acc -- so a logit has the bits both statistics
+// passes saw; where that kernel folds a tile's 32 logits of a lane's row into its statistics, this one writes their confidences.
+// The grid covers Smax rows: a block beyond the problem's rows only writes zeros.
+template <bool VEC>
+__device__ __forceinline__ void feat_conf_body(const float *A, const float *Bm, const int *offA, const int *offB, int C, float alpha,
+                                               const float *lse_r, const float *lse_c, float *conf, int Smax, int Tmax) {
+    __shared__ __attribute__((aligned(16))) float sm[(FM_BM + FM_BN) * FM_LD];
+    __shared__ float sv[FM_BN];
+    const int t = threadIdx.x, b = blockIdx.y;
+    const int a0 = offA[b], S = offA[b + 1] - a0, b0 = offB[b], T = offB[b + 1] - b0;
+    const int r0 = blockIdx.x * FM_BM;
+    conf += (size_t)b * Smax * Tmax;
+    if (r0 >= S) {                                               // (uniform) padding rows
+        const int nr = min(FM_BM, Smax - r0);
+        for (int i = 0; i < nr; ++i)
+            for (int j = t; j < Tmax; j += 256) conf[(size_t)(r0 + i) * Tmax + j] = 0.f;
+        return;
+    }
+    A += (size_t)a0 * C; Bm += (size_t)b0 * C;
+    lse_r += a0; lse_c += b0;
+    const int lane = t & 63, w = t >> 6, li = lane & 31, h = lane >> 5;
+    const int n_kc = (C + FM_KC - 1) / FM_KC, n_jt = (T + FM_BN - 1) / FM_BN, total = n_kc * n_jt;
+    const float4 *pi = reinterpret_cast<const float4 *>(sm + li * FM_LD + 16 * h);
+    const float4 *pj0 = reinterpret_cast<const float4 *>(sm + (FM_BM + w * 64 + li) * FM_LD + 16 * h), *pj1 = pj0 + 32 * FM_LD / 4;
+    float pre[FM_NLOAD], pv = 0.f;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    const int gi = r0 + li;
+    const float lr = gi < S ? lse_r[gi] : 0.f;
+    float *crow = conf + (size_t)gi * Tmax;
+    fm_fetch<VEC>(pre, pv, A, Bm, lse_c, C, S, T, r0, 0, 0);     // v = lse_col: sv holds the tile's column statistics (-inf beyond T)
+    int jt = 0, kc = 0;
+    for (int it = 0; it < total; ++it) {
+        fm_stage<VEC>(pre, sm);
+        if (kc == 0) sv[t] = pv;
+        __syncthreads();
+        int jn = jt, kn = kc + 1;
+        if (kn == n_kc) { kn = 0; ++jn; }
+        if (it + 1 < total) fm_fetch<VEC>(pre, pv, A, Bm, lse_c, C, S, T, r0, jn, kn);
+        const int kp = (min(FM_KC, C - kc * FM_KC) + 1) >> 1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (4 * q < kp) {
+                const float4 bi = pi[q], a0q = pj0[q], a1q = pj1[q];
+                acc0 = MFMA32(a0q.x, bi.x, acc0); acc1 = MFMA32(a1q.x, bi.x, acc1);
+                acc0 = MFMA32(a0q.y, bi.y, acc0); acc1 = MFMA32(a1q.y, bi.y, acc1);
+                acc0 = MFMA32(a0q.z, bi.z, acc0); acc1 = MFMA32(a1q.z, bi.z, acc1);
+                acc0 = MFMA32(a0q.w, bi.w, acc0); acc1 = MFMA32(a1q.w, bi.w, acc1);
+            }
+        }
+        if (kn == 0) {                                           // the tile's last chunk: the 32 confidences of this lane's row
+            if (gi < Smax) {
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    const int jl = w * 64 + (r >> 4) * 32 + (r & 3) + 8 * ((r & 15) >> 2) + 4 * h, j = jt * FM_BN + jl;
+                    const float a = alpha * (r < 16 ? acc0[r & 15] : acc1[r & 15]);
+                    if (j < Tmax) crow[j] = (gi < S && j < T) ? expf(a - lr) * expf(a - sv[jl]) : 0.f;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+        }
+        jt = jn; kc = kn;
+        __syncthreads();
+    }
+    const int nr = min(FM_BM, Smax - r0);                        // the columns behind the last tile
+    for (int i = 0; i < nr; ++i)
+        for (int j = n_jt * FM_BN + t; j < Tmax; j += 256) conf[(size_t)(r0 + i) * Tmax + j] = 0.f;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_feat_conf(const float *A, const float *Bm, const int *offA, const int *offB, int C, float alpha, const float *lse_r, const float *lse_c,
+            float *conf, int Smax, int Tmax) {
+    feat_conf_body<false>(A, Bm, offA, offB, C, alpha, lse_r, lse_c, conf, Smax, Tmax);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_feat_conf_v4(const float *A, const float *Bm, const int *offA, const int *offB, int C, float alpha, const float *lse_r, const float *lse_c,
+               float *conf, int Smax, int Tmax) {
+    feat_conf_body<true>(A, Bm, offA, offB, C, alpha, lse_r, lse_c, conf, Smax, Tmax);
+}
+
+// floats: lse_row [nS], lse_col [nT]
+extern "C" int ndp_feat_conf_workspace(int B, long long nS, long long nT, long long *nbytes) {
+    if (B < 1 || B > NDP_MAX_B || nS < 1 || nT < 1 || nS > 0x7fffffffLL || nT > 0x7fffffffLL || !nbytes)
+        return fail(NDP_E_INVALID, "ndp_feat_conf_workspace: B in 1..65535, 1 <= nS, nT < 2^31, nbytes not NULL");
+    *nbytes = 4 * (nS + nT);
+    return 0;
+}
+
+extern "C" int ndp_feat_conf(const float *fs, const float *ft, const int *offS, const int *offT, const int *offS_host, const int *offT_host,
+                             int B, int C, float temperature, void *ws, float *conf, int Smax, int Tmax, void *stream) {
+    FmShape sh;
+    if (int rc = fm_check("ndp_feat_conf", offS_host, offT_host, B, C, &sh)) return rc;
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail(NDP_E_INVALID, "ndp_feat_conf: temperature must be positive and finite");
+    if (Smax < sh.maxA || Tmax < sh.maxB)
+        return failf(NDP_E_INVALID, "ndp_feat_conf: conf is [B, Smax, Tmax] with Smax >= %d and Tmax >= %d, the largest problem", sh.maxA, sh.maxB);
+    if (!fs || !ft || !offS || !offT || !ws || !conf) return fail(NDP_E_INVALID, "ndp_feat_conf: null pointer");
+    if (!fm_aligned4(fs) || !fm_aligned4(ft) || !fm_aligned4(offS) || !fm_aligned4(offT) || !fm_aligned4(ws) || !fm_aligned4(conf))
+        return fail(NDP_E_INVALID, "ndp_feat_conf: pointers and the workspace must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float *lr = (float *)ws, *lc = lr + sh.nA;
+    const float alpha = 1.f / ((float)C * temperature);          // ndp_feat_match's
+    if (int rc = fm_rowstats_launch(fs, ft, offS, offT, sh.maxA, B, C, alpha, nullptr, nullptr, lr, nullptr, nullptr, s)) return rc;
+    if (int rc = fm_rowstats_launch(ft, fs, offT, offS, sh.maxB, B, C, alpha, nullptr, nullptr, lc, nullptr, nullptr, s)) return rc;
+    const dim3 grid((Smax + FM_BM - 1) / FM_BM, B);
+    if (C % 4 == 0 && aligned16(fs) && aligned16(ft))
+        hipLaunchKernelGGL(k_feat_conf_v4, grid, dim3(256), 0, s, fs, ft, offS, offT, C, alpha, (const float *)lr, (const float *)lc, conf, Smax, Tmax);
+    else
+        hipLaunchKernelGGL(k_feat_conf, grid, dim3(256), 0, s, fs, ft, offS, offT, C, alpha, (const float *)lr, (const float *)lc, conf, Smax, Tmax);
+    HIP_TRY(hipGetLastError(), "k_feat_conf launch");
+    return 0;
+}

@@ -6,9 +6,10 @@ What runs where: every KPConv is one ops.kpconv call (csrc/ndp_kpconv_conv.inc);
 and the two shadow-row gathers (max_pool, closest_pool) are torch ops on the device.  Forward only: ops.kpconv has no backward.
 
 Not served: deformable / modulated convolutions, the `equivariant` / `invariant` block names, any `phase` but "coarse" (the
-reference's fine decoder is commented out upstream; `fine_out` is kept as unused parameters so that checkpoints load), and Lepard's
-repositioning transformer between this backbone and the matching -- descriptors from here go to matching.* as they are.  Parity with
-a trained Lepard checkpoint is unverified: none is available."""
+reference's fine decoder is commented out upstream; `fine_out` is kept as unused parameters so that checkpoints load).  Lepard's
+repositioning transformer between this backbone and the matching is deformationpyramid_amd/lepard.py (lepard.Pipeline holds this
+backbone); descriptors from here go to matching.* as they are only when that is what the caller wants.  Parity with a trained
+Lepard checkpoint is unverified: none is available."""
 import math
 from types import SimpleNamespace
 
@@ -273,7 +274,7 @@ def coarse_features(model, points, lengths, config, neighborhood_limits):
     """Stacked clouds -> (coarse points [n_coarse, 3], their lengths [B] int32 on the host, descriptors [n_coarse, coarse_feature_dim]):
     kpconv.build_pyramid with the config's numbers, ones [N, 1] as input features, model's coarse forward.  Cut per cloud by the
     lengths, the descriptors are what matching.* and matching.landmarks_from_descriptors take.  Lepard's repositioning transformer
-    between the backbone and the matching is NOT applied."""
+    between the backbone and the matching is NOT applied here: lepard.Pipeline / lepard.predict_landmarks apply it."""
     config = _cfg(config)
     batch = kpconv.build_pyramid(points, lengths, config.first_subsampling_dl, config.conv_radius, config.deform_radius,
                                  config.architecture, neighborhood_limits)

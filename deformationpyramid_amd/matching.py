@@ -4,7 +4,8 @@ dustbin, then the mutual-maximum test of `get_match`) and its feature-matching h
 `mutual_selection`, `get_inlier_ratio`), without their S x T matrices: the kernels keep row and column statistics only.
 
 The inputs are the feature matrices the reference hands to its matcher AFTER `src_proj` and the positional embedding; the learned
-layers are not part of this package.  Scores follow the reference: <fs_i, ft_j> / C (its `feat / C ** .5` on both sides), so
+layers in front of them (the repositioning transformer, `src_proj`, the rotary embedding) are deformationpyramid_amd/lepard.py, whose
+`Matching` also returns the dense confidence matrix (ops.feat_conf).  Scores follow the reference: <fs_i, ft_j> / C (its `feat / C ** .5` on both sides), so
 unit-norm descriptors (FCGF, Predator, FPFH after normalisation) want a factor sqrt(C) first to make `temperature` act on cosines.
 
 Ties: where the reference's `conf == conf.max()` test accepts every column that attains a row's maximum, the kernels take the lowest

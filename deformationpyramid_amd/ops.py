@@ -504,6 +504,63 @@ def feat_match(fs, ft, mode="dual_softmax", temperature=0.1, bin_score=1.0, iter
     return match_t, conf
 
 
+def feat_conf(fs, ft, temperature=0.1, offsets_s=None, offsets_t=None):
+    """The dense dual-softmax confidence matrix of descriptors fs [sum S,C] and ft [sum T,C] (csrc/ndp_match.inc: ndp_feat_conf, two
+    k_feat_rowstats launches and one dense pass) -> conf [B, Smax, Tmax]: softmax over i times softmax over j of
+    <fs_i, ft_j> / (C temperature) inside each problem's S x T, exactly 0 in the padding (the reference's masked batch,
+    matching.py:144-157).  Does not synchronise."""
+    B, C, os_, ot, hs, ht = _feat_problems(fs, ft, offsets_s, offsets_t)
+    dev = fs.device
+    smax = max(hs[b + 1] - hs[b] for b in range(B))
+    tmax = max(ht[b + 1] - ht[b] for b in range(B))
+    ws = _workspace("ndp_feat_conf_workspace", (B, fs.shape[0], ft.shape[0]), dev, torch.float32, per=4)
+    conf = torch.empty(B, smax, tmax, device=dev)
+    N.check(N.lib().ndp_feat_conf(_p(fs), _p(ft), _p(os_), _p(ot), hs, ht, B, C, float(temperature), _p(ws), _p(conf), smax, tmax,
+                                  N.stream_ptr(dev)), "ndp_feat_conf")
+    return conf
+
+
+def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None):
+    """Multi-head soft-max attention of stacked, unpadded problems (csrc/ndp_attention.inc: one fused launch, scores and P V on the
+    f32-input MFMA, the L x S x H scores are never stored) -> o [sum L, C].  q [sum L,C], k, v [sum S,C] already projected (made
+    contiguous if they are not); head h owns the channels h D .. h D + D - 1, D = C / n_head.  pe_q [sum L,C,2], pe_k [sum S,C,2]:
+    the (cos, sin) of a rotary code per channel (lepard.VolumetricPositionEncoding), both or neither; q and k are rotated while they
+    are staged, v is not.  scale defaults to D ** -0.5.  offsets_*: B + 1 ascending row offsets for B problems in one call.  Forward
+    only; does not synchronise."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.ndim != 2:
+            raise ValueError(f"{name} must be a tensor [rows, C], got {getattr(t, 'shape', type(t))}")
+    C, n_head = q.shape[1], int(n_head)
+    if k.shape[1] != C or v.shape[1] != C or k.shape[0] != v.shape[0]:
+        raise ValueError(f"q [L,C], k [S,C] and v [S,C] must agree, got {tuple(q.shape)}, {tuple(k.shape)} and {tuple(v.shape)}")
+    if n_head < 1 or C < 1 or C % n_head != 0:
+        raise ValueError(f"C = {C} must be a positive multiple of n_head = {n_head}")
+    D = C // n_head
+    if (pe_q is None) != (pe_k is None):
+        raise ValueError("pe_q and pe_k are passed as both or neither")
+    if pe_q is not None:
+        if D % 2 != 0:
+            raise ValueError(f"a rotary code needs an even head dimension, got C / n_head = {D}")
+        for t, ref, name in ((pe_q, q, "pe_q"), (pe_k, k, "pe_k")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (ref.shape[0], C, 2):
+                raise ValueError(f"{name} must be [{ref.shape[0]}, {C}, 2], got {getattr(t, 'shape', type(t))}")
+    scale = D ** -0.5 if scale is None else float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"scale must be finite, got {scale}")
+    q, k, v = (_chk(t.contiguous() if isinstance(t, torch.Tensor) and t.is_cuda else t, name) for t, name in ((q, "q"), (k, "k"), (v, "v")))
+    if pe_q is not None:
+        pe_q, pe_k = _chk(pe_q.contiguous() if pe_q.is_cuda else pe_q, "pe_q"), _chk(pe_k.contiguous() if pe_k.is_cuda else pe_k, "pe_k")
+    dev = q.device
+    oq, hq = _host_offsets(q.shape[0], offsets_q, "offsets_q", dev)
+    ok, hk = _host_offsets(k.shape[0], offsets_k, "offsets_k", dev)
+    if len(hq) != len(hk):
+        raise ValueError(f"both sides must list the same problems, got {len(hq) - 1} and {len(hk) - 1}")
+    out = torch.empty_like(q)
+    N.check(N.lib().ndp_attention_forward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(oq), _p(ok), hq, hk, len(hq) - 1, C, n_head, scale,
+                                          _p(out), N.stream_ptr(dev)), "ndp_attention_forward")
+    return out
+
+
 RADIUS_MAX_K = 64
 
 

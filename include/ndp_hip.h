@@ -433,6 +433,37 @@ int ndp_kpconv_forward(const float *q, const float *s, const int *idx, const flo
                        long long nq, long long ns, int H, int K, int cin, int cout, float extent, int influence, int aggregation,
                        int normalize, void *ws, long long ws_bytes, float *y, void *stream);
 
+/* Attention and the dense confidence matrix (csrc/ndp_attention.inc, the end of csrc/ndp_match.inc; DESIGN.md "Attention"), ABI 215:
+ * what Lepard's repositioning transformer (correspondence/lepard/transformer.py, matching.py) needs between the KPFCN descriptors
+ * and the match list.  Problems are stacked and unpadded as for ndp_feat_rowstats: problem b owns the rows off[b] .. off[b + 1];
+ * the offsets are given twice, on the device and as a HOST copy which the entry checks before anything is launched.
+ *
+ * ndp_attention_forward: multi-head soft-max attention.  q [sum L][C], k, v [sum S][C] fp32, already projected; D = C / n_head;
+ *   pe_q [sum L][C][2], pe_k [sum S][C][2]: (cos, sin) per channel of a rotary code, both or neither (NULL).
+ *     o[i, h D + d] = sum_j softmax_j(scale <q'_i,h, k'_j,h>) v[j, h D + d]
+ *     q' = q cos + rot(q) sin, rot(x)[2m] = -x[2m + 1], rot(x)[2m + 1] = x[2m] (VolumetricPositionEncoding.embed_rotary); v is not
+ *     rotated.  The rotation is applied while an operand is staged: no rotated copy and no L x S x H score reaches global memory.
+ *   One launch; scores and P V on the f32-input MFMA (exact fp32 products, one rounding per term), an online soft-max over key
+ *   tiles in ascending order, every partial result folded in one fixed order, no atomics.  No bit of an output row depends on the
+ *   other problems of the call, on the other query rows, or on where the row falls in its block.  Nothing is data-dependent: the
+ *   entry DOES NOT synchronise.  No backward pass.
+ *   NDP_E_UNSUPPORTED: outside 1 <= C <= 1056, 1 <= n_head <= 16 with C % n_head == 0 and C / n_head <= 264, rows <= 2^30 a side.
+ *   NDP_E_INVALID: B outside 1..65535, bad offsets (negative, not monotone, an empty side), a NULL or misaligned pointer, one of
+ *   pe_q / pe_k without the other, a rotary code with an odd C / n_head, a scale that is not finite.
+ * ndp_feat_conf: the dense dual-softmax confidence matrix conf [B][Smax][Tmax] (Smax, Tmax at least the largest problem's S, T):
+ *     conf[b, i, j] = exp(a_ij - lse_row_i) exp(a_ij - lse_col_j),  a_ij = <fs_i, ft_j> / (C temperature)
+ *   inside a problem's S x T and exactly 0 outside it (matching.py:144-157 on a padded batch).  Two ndp_feat_rowstats launches
+ *   for the statistics, then one dense pass that recomputes a_ij with that kernel's operand order and chain.  Does not synchronise.
+ *   ws: ndp_feat_conf_workspace(B, sum S, sum T) bytes, 4-byte aligned; the query needs no device.
+ *   NDP_E_INVALID: as ndp_feat_rowstats, temperature not positive and finite, Smax / Tmax below the largest problem.
+ *   Sinkhorn confidences are not served as a matrix.                                                                              */
+int ndp_attention_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ,
+                          const int *offK, const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale,
+                          float *o, void *stream);
+int ndp_feat_conf_workspace(int B, long long nS, long long nT, long long *nbytes);
+int ndp_feat_conf(const float *fs, const float *ft, const int *offS, const int *offT, const int *offS_host, const int *offT_host,
+                  int B, int C, float temperature, void *ws, float *conf, int Smax, int Tmax, void *stream);
+
 /* Landmark loss mean_k |x_k - t_k|^2 and gradient (registration.py:201-203). */
 int ndp_landmark_mse_fwd_bwd(const float *x, const float *t, int K, float *loss, float *gx, void *stream);
 

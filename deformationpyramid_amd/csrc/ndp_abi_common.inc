@@ -101,7 +101,8 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 //   213: ndp_voxel_subsample_workspace, ndp_voxel_subsample, ndp_radius_search_workspace, ndp_radius_search
 //   214: ndp_kpconv_forward_workspace, ndp_kpconv_forward
 //   215: ndp_attention_forward, ndp_feat_conf_workspace, ndp_feat_conf
-extern "C" int ndp_version(void) { return 215; }
+//   216: ndp_attention_compat_forward
+extern "C" int ndp_version(void) { return 216; }
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }

@@ -17,12 +17,24 @@
 // the query (two xor shuffles; a maximum has no order), the running sum stays a per-lane partial.  Channels D .. DP - 1 (DP = D
 // rounded up to 4) and rows beyond the problem are zeros in LDS, never reads; a key beyond S scores -inf.  At the end the four waves'
 // (m, s, O) of a query are folded in wave order, each wave's four partial sums in lane-group order.
+//
+// COMPAT (k_attention_compat_*, ndp_attention_compat_forward; DESIGN.md "Outlier rejection"): the score of (i, j, h) is multiplied by
+// the spatial compatibility of the correspondences i and j before the scale and the soft-max,
+//   c[i, j] = max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_spat^2),      pos [rows, 6] = (s_xyz, t_xyz) per row
+// in fp32 and in the reference's order of operations (outlier_rejection/pipeline.py:55-58): the norm of the source difference, the
+// norm of the target difference, their difference squared, a true division by (float)(sigma_spat^2), 1 minus that, clamped at 0;
+// sqrtf and the division are correctly rounded.  The key tile's 64 x 6 positions are staged in LDS behind the statistics, the lane's
+// own query row's six coordinates stay in registers for the whole walk, and c is taken for the lane's four score registers between
+// the score chain and the online soft-max.  c depends on (i, j) only and is recomputed per head: about 20 vector operations against
+// D multiply-adds per pair.  c = 0 scores 0, not -inf: such a key takes part in the soft-max.  A key beyond S still scores -inf.
+// Non-finite positions are the caller's error and are not checked on the device.
 #define AT_BM 16
 #define AT_BN 64
 #define AT_MAX_H 16
 #define AT_MAX_D 264
 #define AT_STATS 512                   // floats behind the tiles: the waves' m [4][16], s [4][4][16], the fold's factors [4][16] and sums [16]
 #define AT_MAX_ROWS (1 << 30)
+#define AT_POS 6                       // floats of a correspondence's position row (COMPAT): source xyz, target xyz
 
 // LDS row stride in words for DP channels: a multiple of 4 that is 4 modulo 8, so 16 rows x 4 consecutive words spread over the banks
 __host__ __device__ static inline int at_ld(int DP) { return DP % 8 == 0 ? DP + 4 : DP; }
@@ -68,9 +80,16 @@ __device__ __forceinline__ void at_stage(float *dst, int LD, const float *src, c
     }
 }
 
-template <int NT, bool VEC>
+// |a - b| of two points in the reference's order: the three squares summed in axis order, one correctly rounded square root
+__device__ __forceinline__ float at_dist(const float *a, const float *b) {
+    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+
+template <int NT, bool VEC, bool COMPAT>
 __device__ __forceinline__ void attention_body(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k,
-                                               const int *offQ, const int *offK, int C, int D, float scale, float *out) {
+                                               const float *pos_q, const float *pos_k, const int *offQ, const int *offK, int C, int D,
+                                               float scale, float sigma2, float *out) {
     extern __shared__ __attribute__((aligned(16))) float at_sm[];
     const int t = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int q0 = offQ[b], L = offQ[b + 1] - q0, k0 = offK[b], S = offK[b + 1] - k0;
@@ -84,12 +103,22 @@ __device__ __forceinline__ void attention_body(const float *q, const float *k, c
 #pragma unroll
     for (int dt = 0; dt < NT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, s = 0.f;                                // query l15 over the keys this wave has met; s: this lane's share
+    float *Ps = st + AT_STATS;                                   // COMPAT: [AT_BN][AT_POS], the key tile's positions
+    float pq[AT_POS];                                            // COMPAT: query l15's own position (zeros beyond L: that row is never written)
+    if (COMPAT) {
+#pragma unroll
+        for (int u = 0; u < AT_POS; ++u) pq[u] = r0 + l15 < L ? pos_q[((size_t)q0 + r0 + l15) * AT_POS + u] : 0.f;
+    }
     const int n_jt = (S + AT_BN - 1) / AT_BN;
     for (int jt = 0; jt < n_jt; ++jt) {
         if (jt) __syncthreads();
         const int nv = min(AT_BN, S - jt * AT_BN), nrows = (nv + 15) & ~15;
         at_stage<VEC>(Ks, LD, k, pe_k, C, ch0, D, DP, (size_t)k0 + jt * AT_BN, nv, nrows);
         at_stage<VEC>(Vs, LD, v, nullptr, C, ch0, D, DP, (size_t)k0 + jt * AT_BN, nv, nrows);
+        if (COMPAT) {                                            // the tile's position rows are contiguous; zeros beyond the problem
+            for (int idx = t; idx < AT_BN * AT_POS; idx += 256)
+                Ps[idx] = idx < nv * AT_POS ? pos_k[((size_t)k0 + jt * AT_BN) * AT_POS + idx] : 0.f;
+        }
         __syncthreads();
         if (16 * w < nv) {                                       // (uniform per wave) this wave's 16 keys hold at least one of the problem
             f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -98,7 +127,13 @@ __device__ __forceinline__ void attention_body(const float *q, const float *k, c
             float x[4], tm = -INFINITY;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                x[r] = 16 * w + 4 * g + r < nv ? scale * sc[r] : -INFINITY;
+                float a = sc[r];
+                if (COMPAT) {
+                    const float *pk = Ps + (16 * w + 4 * g + r) * AT_POS;
+                    const float dd = at_dist(pq, pk) - at_dist(pq + 3, pk + 3);
+                    a *= fmaxf(0.f, 1.0f - (dd * dd) / sigma2);
+                }
+                x[r] = 16 * w + 4 * g + r < nv ? scale * a : -INFINITY;
                 tm = fmaxf(tm, x[r]);
             }
             tm = fmaxf(tm, __shfl_xor(tm, 16));
@@ -174,7 +209,7 @@ __device__ __forceinline__ void attention_body(const float *q, const float *k, c
     extern "C" __global__ void __launch_bounds__(256)                                                                           \
     name(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ, const int *offK, int C, \
          int D, float scale, float *out) {                                                                                      \
-        attention_body<NT, VEC>(q, k, v, pe_q, pe_k, offQ, offK, C, D, scale, out);                                             \
+        attention_body<NT, VEC, false>(q, k, v, pe_q, pe_k, nullptr, nullptr, offQ, offK, C, D, scale, 0.f, out);               \
     }
 AT_KERNEL(k_attention_d16, 1, false)
 AT_KERNEL(k_attention_d48, 3, false)
@@ -185,19 +220,34 @@ AT_KERNEL(k_attention_d48_v4, 3, true)
 AT_KERNEL(k_attention_d144_v4, 9, true)
 AT_KERNEL(k_attention_d264_v4, 17, true)
 #undef AT_KERNEL
+#define AT_KERNEL(name, NT, VEC)                                                                                                \
+    extern "C" __global__ void __launch_bounds__(256)                                                                           \
+    name(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const float *pos_q, const float *pos_k, \
+         const int *offQ, const int *offK, int C, int D, float scale, float sigma2, float *out) {                               \
+        attention_body<NT, VEC, true>(q, k, v, pe_q, pe_k, pos_q, pos_k, offQ, offK, C, D, scale, sigma2, out);                 \
+    }
+AT_KERNEL(k_attention_compat_d16, 1, false)
+AT_KERNEL(k_attention_compat_d48, 3, false)
+AT_KERNEL(k_attention_compat_d144, 9, false)
+AT_KERNEL(k_attention_compat_d264, 17, false)
+AT_KERNEL(k_attention_compat_d16_v4, 1, true)
+AT_KERNEL(k_attention_compat_d48_v4, 3, true)
+AT_KERNEL(k_attention_compat_d144_v4, 9, true)
+AT_KERNEL(k_attention_compat_d264_v4, 17, true)
+#undef AT_KERNEL
 
 // ------------------------------------------------------------------------------------------------
-// host entry.  Every refusal is decided before the first HIP call; nothing in the entry is data-dependent, so it does not synchronise.
-extern "C" int ndp_attention_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ,
-                                     const int *offK, const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale,
-                                     float *out, void *stream) {
-    const char *who = "ndp_attention_forward";
+// host entries.  Every refusal is decided before the first HIP call; nothing in an entry is data-dependent, so it does not synchronise.
+// The refusals both entries share -> 0 with the largest L and whether the 16-byte staging serves the call.
+static int at_check(const char *who, const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ,
+                    const int *offK, const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale, const float *out,
+                    int *maxL, bool *vec) {
     if (int rc = check_batch(who, offQ_host && offK_host ? offQ_host : nullptr, B)) return rc;
     if (C < 1 || C > FM_MAX_C || n_head < 1 || n_head > AT_MAX_H || C % n_head != 0 || C / n_head > AT_MAX_D)
         return failf(NDP_E_UNSUPPORTED, "%s: served are 1 <= C <= %d, 1 <= n_head <= %d with C a multiple of n_head and C / n_head <= %d", who,
                      FM_MAX_C, AT_MAX_H, AT_MAX_D);
-    int maxL = 0, maxS = 0;
-    if (int rc = check_offsets(who, offQ_host, B, 1, "a non-empty side, L and S", &maxL)) return rc;
+    int maxS = 0;
+    if (int rc = check_offsets(who, offQ_host, B, 1, "a non-empty side, L and S", maxL)) return rc;
     if (int rc = check_offsets(who, offK_host, B, 1, "a non-empty side, L and S", &maxS)) return rc;
     if (offQ_host[B] > AT_MAX_ROWS || offK_host[B] > AT_MAX_ROWS) return failf(NDP_E_UNSUPPORTED, "%s: served are at most 2^30 rows a side", who);
     if (!q || !k || !v || !offQ || !offK || !out) return failf(NDP_E_INVALID, "%s: null pointer", who);
@@ -208,16 +258,59 @@ extern "C" int ndp_attention_forward(const float *q, const float *k, const float
     const int D = C / n_head;
     if (pe_q && D % 2 != 0) return failf(NDP_E_INVALID, "%s: a rotary code needs an even head dimension (C / n_head = %d)", who, D);
     if (!std::isfinite(scale)) return failf(NDP_E_INVALID, "%s: scale must be finite", who);
-    const bool vec = D % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(pe_q) && aligned16(pe_k);
+    *vec = D % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(pe_q) && aligned16(pe_k);
+    return 0;
+}
+
+static const int at_dmax[4] = {16, 48, 144, 264};
+static inline int at_class(int D) { return D <= 16 ? 0 : D <= 48 ? 1 : D <= 144 ? 2 : 3; }
+
+extern "C" int ndp_attention_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ,
+                                     const int *offK, const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale,
+                                     float *out, void *stream) {
+    int maxL = 0;
+    bool vec = false;
+    if (int rc = at_check("ndp_attention_forward", q, k, v, pe_q, pe_k, offQ, offK, offQ_host, offK_host, B, C, n_head, scale, out, &maxL, &vec))
+        return rc;
+    const int D = C / n_head, cls = at_class(D);
     using Kern = void (*)(const float *, const float *, const float *, const float *, const float *, const int *, const int *, int, int, float, float *);
-    const int cls = D <= 16 ? 0 : D <= 48 ? 1 : D <= 144 ? 2 : 3;
     static const Kern kern[2][4] = {{k_attention_d16, k_attention_d48, k_attention_d144, k_attention_d264},
                                     {k_attention_d16_v4, k_attention_d48_v4, k_attention_d144_v4, k_attention_d264_v4}};
-    static const int dmax[4] = {16, 48, 144, 264};
     const Kern fn = kern[vec][cls];
-    if (int rc = set_smem((const void *)fn, 4 * at_lds_floats(dmax[cls]))) return rc;
+    if (int rc = set_smem((const void *)fn, 4 * at_lds_floats(at_dmax[cls]))) return rc;
     const dim3 grid((maxL + AT_BM - 1) / AT_BM, n_head, B);
     hipLaunchKernelGGL(fn, grid, dim3(256), 4 * at_lds_floats(D), (hipStream_t)stream, q, k, v, pe_q, pe_k, offQ, offK, C, D, scale, out);
     HIP_TRY(hipGetLastError(), "k_attention launch");
+    return 0;
+}
+
+// The compatibility-modulated form: pos_q [sum L][6], pos_k [sum S][6] are always both taken; sigma_spat is a double so that
+// (float)(sigma_spat^2) is the divisor the reference's `** 2 / self.sigma_spat ** 2` rounds to.  +inf is served and means c == 1.
+extern "C" int ndp_attention_compat_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k,
+                                            const float *pos_q, const float *pos_k, const int *offQ, const int *offK, const int *offQ_host,
+                                            const int *offK_host, int B, int C, int n_head, float scale, double sigma_spat, float *out,
+                                            void *stream) {
+    const char *who = "ndp_attention_compat_forward";
+    int maxL = 0;
+    bool vec = false;
+    if (int rc = at_check(who, q, k, v, pe_q, pe_k, offQ, offK, offQ_host, offK_host, B, C, n_head, scale, out, &maxL, &vec)) return rc;
+    if (!pos_q || !pos_k) return failf(NDP_E_INVALID, "%s: null pointer (pos_q and pos_k are always both taken)", who);
+    if (!fm_aligned4(pos_q) || !fm_aligned4(pos_k)) return failf(NDP_E_INVALID, "%s: pointers must be 4-byte aligned", who);
+    if (!(sigma_spat > 0)) return failf(NDP_E_INVALID, "%s: sigma_spat must be positive (inf: no compatibility), got %g", who, sigma_spat);
+    const float sigma2 = (float)(sigma_spat * sigma_spat);
+    if (!(sigma2 > 0)) return failf(NDP_E_INVALID, "%s: sigma_spat^2 = %g^2 underflows float32", who, sigma_spat);
+    const int D = C / n_head, cls = at_class(D);
+    using Kern = void (*)(const float *, const float *, const float *, const float *, const float *, const float *, const float *, const int *,
+                          const int *, int, int, float, float, float *);
+    static const Kern kern[2][4] = {
+        {k_attention_compat_d16, k_attention_compat_d48, k_attention_compat_d144, k_attention_compat_d264},
+        {k_attention_compat_d16_v4, k_attention_compat_d48_v4, k_attention_compat_d144_v4, k_attention_compat_d264_v4}};
+    const Kern fn = kern[vec][cls];
+    const int pos_floats = AT_BN * AT_POS;                       // the key tile's positions, behind the statistics
+    if (int rc = set_smem((const void *)fn, 4 * (at_lds_floats(at_dmax[cls]) + pos_floats))) return rc;
+    const dim3 grid((maxL + AT_BM - 1) / AT_BM, n_head, B);
+    hipLaunchKernelGGL(fn, grid, dim3(256), 4 * (at_lds_floats(D) + pos_floats), (hipStream_t)stream, q, k, v, pe_q, pe_k, pos_q, pos_k, offQ,
+                       offK, C, D, scale, sigma2, out);
+    HIP_TRY(hipGetLastError(), "k_attention_compat launch");
     return 0;
 }

@@ -324,16 +324,22 @@ class Pipeline(nn.Module):
 
 
 @torch.no_grad()
-def predict_landmarks(pipeline, src, tgt, neighborhood_limits):
-    """Two clouds src [N,3], tgt [M,3] on the device -> (ldmk_s [K,3], ldmk_t [K,3], conf [K], R [3,3], t [3]): the coarse points of
-    the pipeline's mutual matches in ascending source order with their confidences, and the soft-Procrustes pose.  The landmarks are
-    what Registration.load_pcds(..., landmarks=) and rigid.reject_landmarks take."""
+def run_pair(pipeline, src, tgt, neighborhood_limits):
+    """Two clouds src [N,3], tgt [M,3] on the device -> the pipeline's batch of that one pair (Pipeline.forward's keys)."""
     kcfg = _get(pipeline.config, "kpfcn_config")
     points = torch.cat([src, tgt]).float().contiguous()
     batch = kpconv.build_pyramid(points, [src.shape[0], tgt.shape[0]], _get(kcfg, "first_subsampling_dl"), _get(kcfg, "conv_radius"),
                                  _get(kcfg, "deform_radius"), _get(kcfg, "architecture"), neighborhood_limits)
     batch["features"] = torch.ones(points.shape[0], 1, device=points.device)
-    out = pipeline(batch)
+    return pipeline(batch)
+
+
+@torch.no_grad()
+def predict_landmarks(pipeline, src, tgt, neighborhood_limits):
+    """Two clouds src [N,3], tgt [M,3] on the device -> (ldmk_s [K,3], ldmk_t [K,3], conf [K], R [3,3], t [3]): the coarse points of
+    the pipeline's mutual matches in ascending source order with their confidences, and the soft-Procrustes pose.  The landmarks are
+    what Registration.load_pcds(..., landmarks=), rigid.reject_landmarks and outlier.reject_landmarks take."""
+    out = run_pair(pipeline, src, tgt, neighborhood_limits)
     index = out["coarse_match_pred"]
     i, j = index[:, 1], index[:, 2]
     return (out["s_pcd"][i].contiguous(), out["t_pcd"][j].contiguous(), out["conf_matrix_pred"][0, i, j], out["R_s2t_pred"][0],

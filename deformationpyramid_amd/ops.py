@@ -520,13 +520,16 @@ def feat_conf(fs, ft, temperature=0.1, offsets_s=None, offsets_t=None):
     return conf
 
 
-def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None):
+def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None, pos_q=None, pos_k=None, sigma_spat=None):
     """Multi-head soft-max attention of stacked, unpadded problems (csrc/ndp_attention.inc: one fused launch, scores and P V on the
     f32-input MFMA, the L x S x H scores are never stored) -> o [sum L, C].  q [sum L,C], k, v [sum S,C] already projected (made
     contiguous if they are not); head h owns the channels h D .. h D + D - 1, D = C / n_head.  pe_q [sum L,C,2], pe_k [sum S,C,2]:
     the (cos, sin) of a rotary code per channel (lepard.VolumetricPositionEncoding), both or neither; q and k are rotated while they
-    are staged, v is not.  scale defaults to D ** -0.5.  offsets_*: B + 1 ascending row offsets for B problems in one call.  Forward
-    only; does not synchronise."""
+    are staged, v is not.  scale defaults to D ** -0.5.  offsets_*: B + 1 ascending row offsets for B problems in one call.
+    pos_q [sum L,6], pos_k [sum S,6] float32 and sigma_spat, all three or none: every score is multiplied by the spatial compatibility
+    max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_spat^2) of the rows' (s_xyz, t_xyz) before the scale and the soft-max
+    (ndp_attention_compat_forward, outlier.CorrespondenceAttentionLayer); sigma_spat = inf is the plain call's bits.  Forward only;
+    does not synchronise."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, torch.Tensor) or t.ndim != 2:
             raise ValueError(f"{name} must be a tensor [rows, C], got {getattr(t, 'shape', type(t))}")
@@ -547,6 +550,16 @@ def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None,
     scale = D ** -0.5 if scale is None else float(scale)
     if not math.isfinite(scale):
         raise ValueError(f"scale must be finite, got {scale}")
+    compat = pos_q is not None or pos_k is not None or sigma_spat is not None
+    if compat:
+        if pos_q is None or pos_k is None or sigma_spat is None:
+            raise ValueError("pos_q, pos_k and sigma_spat are passed all together or not at all")
+        for t, ref, name in ((pos_q, q, "pos_q"), (pos_k, k, "pos_k")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (ref.shape[0], 6):
+                raise ValueError(f"{name} must be [{ref.shape[0]}, 6] (source xyz, target xyz), got {getattr(t, 'shape', type(t))}")
+        sigma_spat = float(sigma_spat)
+        if not sigma_spat > 0:
+            raise ValueError(f"sigma_spat must be positive (inf: no compatibility), got {sigma_spat}")
     q, k, v = (_chk(t.contiguous() if isinstance(t, torch.Tensor) and t.is_cuda else t, name) for t, name in ((q, "q"), (k, "k"), (v, "v")))
     if pe_q is not None:
         pe_q, pe_k = _chk(pe_q.contiguous() if pe_q.is_cuda else pe_q, "pe_q"), _chk(pe_k.contiguous() if pe_k.is_cuda else pe_k, "pe_k")
@@ -556,6 +569,12 @@ def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None,
     if len(hq) != len(hk):
         raise ValueError(f"both sides must list the same problems, got {len(hq) - 1} and {len(hk) - 1}")
     out = torch.empty_like(q)
+    if compat:
+        pos_q, pos_k = _chk(pos_q.contiguous() if pos_q.is_cuda else pos_q, "pos_q"), _chk(pos_k.contiguous() if pos_k.is_cuda else pos_k, "pos_k")
+        N.check(N.lib().ndp_attention_compat_forward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(pos_q), _p(pos_k), _p(oq), _p(ok), hq, hk,
+                                                     len(hq) - 1, C, n_head, scale, sigma_spat, _p(out), N.stream_ptr(dev)),
+                "ndp_attention_compat_forward")
+        return out
     N.check(N.lib().ndp_attention_forward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(oq), _p(ok), hq, hk, len(hq) - 1, C, n_head, scale,
                                           _p(out), N.stream_ptr(dev)), "ndp_attention_forward")
     return out

@@ -18,6 +18,10 @@ feat_s, feat_t`; without the dataset seeded descriptors are planted on the synth
 `--rigid-landmarks THR` (off by default; without it the output is unchanged) also runs RANSAC on every pair's landmarks
 (`deformationpyramid_amd/rigid.py`) and prints a `rigid-*` row -- how much of the ground-truth flow one rigid motion explains -- with
 the mean inlier ratio; `--rigid-landmarks-filter` then registers on the inlier landmarks only.
+`--outlier-weights FILE [--outlier-thr 0.5]` (off by default; without it the output is unchanged) passes every pair's landmarks --
+precomputed, matched from descriptors or synthetic -- through the reference's learned outlier filter (`Landmark_Model.inference`'s
+`vec_6d[inlier_conf > inlier_thr]`, deformationpyramid_amd/outlier.py) before anything else sees them, and prints the mean kept share;
+FILE is the reference's `{'state_dict': ...}` checkpoint of `Outlier_Rejection` at configs/outlier_rejection.yaml.
 """
 import argparse
 import os
@@ -51,7 +55,29 @@ def make_parser():
                          "without the dataset, seeded descriptors planted on the synthetic pairs' landmark points")
     ap.add_argument("--match-type", type=str, default="dual_softmax", choices=["dual_softmax", "sinkhorn", "mutual_nn"],
                     help="with --descriptors: the matcher (deformationpyramid_amd/matching.py)")
+    ap.add_argument("--outlier-weights", type=str, default=None, metavar="FILE",
+                    help="filter every pair's landmarks with the learned outlier rejection network: its {'state_dict': ...} checkpoint")
+    ap.add_argument("--outlier-thr", type=float, default=0.5, help="with --outlier-weights: keep the landmarks whose inlier confidence exceeds this")
     return ap
+
+
+def outlier_rows(items, weights, thr):
+    """The learned outlier filter on every pair's landmarks (deformationpyramid_amd/outlier.py) -> (kept shares, items with the
+    landmarks filtered; a pair that would keep fewer than 3 keeps all of them)."""
+    from deformationpyramid_amd import outlier
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model = outlier.Outlier_Rejection(outlier.DEFAULT_CONFIG)
+    model.load_state_dict(torch.load(weights, map_location="cpu")["state_dict"], strict=True)
+    model = model.to(dev).eval()
+    shares, out = [], []
+    for src, tgt, flow_gt, overlap, (ls, lt) in items:
+        keep, _ = outlier.reject_landmarks(model, ls, lt, thr)
+        keep = keep.cpu()
+        shares.append(float(keep.float().mean()) if keep.numel() else 0.0)
+        if int(keep.sum()) >= 3:
+            ls, lt = ls[keep].contiguous(), lt[keep].contiguous()
+        out.append((src, tgt, flow_gt, overlap, (ls, lt)))
+    return shares, out
 
 
 def descriptor_landmarks(d, match_type):
@@ -120,6 +146,15 @@ def main():
                 items.append((src, tgt, flow_gt, overlap, ldmk))
             if rank == 0 and args.descriptors:
                 print(f"landmarks matched from descriptors ({args.match_type}): {sum(l[4][0].shape[0] for l in items) / max(len(items), 1):.1f} per pair")
+        if args.outlier_weights:
+            kept, items = outlier_rows(items, args.outlier_weights, args.outlier_thr)
+            meters = {"outlier-kept_share": AverageMeter()}
+            for share in kept:
+                meters["outlier-kept_share"].update(share)
+            keys, avgs = reduce_meters(meters, len(items), world, local_rank, backend)
+            if rank == 0:
+                print("learned outlier rejection of the landmarks, thr =", args.outlier_thr, "\n",
+                      f"{n_total}/{n_total}: " + "".join(f"{k}: {avgs[k]:.3f}\t" for k in keys))
         rigid_flows = None
         if args.rigid_landmarks > 0:
             rigid_flows, inlier_ratios, items = rigid_rows(items, args.rigid_landmarks, args.rigid_landmarks_filter)

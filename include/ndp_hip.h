@@ -460,6 +460,20 @@ int ndp_kpconv_forward(const float *q, const float *s, const int *idx, const flo
 int ndp_attention_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const int *offQ,
                           const int *offK, const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale,
                           float *o, void *stream);
+/* ndp_attention_compat_forward (ABI 216; DESIGN.md "Outlier rejection"): ndp_attention_forward with every score multiplied by the
+ * spatial compatibility of the correspondences i and j before the scale and the soft-max -- what the nine layers of the reference's
+ * Outlier_Rejection (correspondence/outlier_rejection/pipeline.py:52-58, geometry_attention.py:85-96) compute on M x M tensors:
+ *     score[i, j, h] = scale (<q'_i,h, k'_j,h> c[i, j]),   c[i, j] = max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_spat^2)
+ *   pos_q [sum L][6], pos_k [sum S][6] fp32: (s_xyz, t_xyz) of every row, always both.  c is taken in fp32 in the reference's order
+ *   (two norms, their difference squared, a true division by (float)(sigma_spat^2), 1 minus, clamp at 0) with correctly rounded
+ *   square roots and division, on the chip: no M x M array exists.  c = 0 scores 0 and takes part in the soft-max; a key beyond S
+ *   scores -inf.  sigma_spat = +inf means c == 1: the bits of ndp_attention_forward.  Every promise of ndp_attention_forward holds.
+ *   Non-finite positions are the caller's error and are not checked on the device.
+ *   Refused as ndp_attention_forward, and NDP_E_INVALID: pos_q or pos_k NULL or misaligned, sigma_spat NaN or <= 0 (or so small
+ *   that its square underflows fp32).                                                                                              */
+int ndp_attention_compat_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k,
+                                 const float *pos_q, const float *pos_k, const int *offQ, const int *offK, const int *offQ_host,
+                                 const int *offK_host, int B, int C, int n_head, float scale, double sigma_spat, float *o, void *stream);
 int ndp_feat_conf_workspace(int B, long long nS, long long nT, long long *nbytes);
 int ndp_feat_conf(const float *fs, const float *ft, const int *offS, const int *offT, const int *offS_host, const int *offT_host,
                   int B, int C, float temperature, void *ws, float *conf, int Smax, int Tmax, void *stream);

@@ -256,9 +256,12 @@ _SIGS = {
     "ndp_attention_compat_forward": [V, V, V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, ctypes.c_double, V, V],
     "ndp_feat_conf_workspace": [I, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_feat_conf": [V, V, V, V, c_int_p, c_int_p, I, I, F, V, V, I, I, V],
+    "ndp_attention_forward_lse": [V, V, V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, ctypes.c_double, V, V, V],
+    "ndp_attention_backward": [V, V, V, V, V, V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, ctypes.c_double, V, V, V, V, V],
 }
 ABI_VERSION = 215                                   # the ABI this signature table was last renumbered at; entries added since (216:
-                                                    # ndp_attention_compat_forward) only append, and ndp_version() tells what a library has
+                                                    # ndp_attention_compat_forward; 217: ndp_attention_forward_lse, ndp_attention_backward)
+                                                    # only append, and ndp_version() tells what a library has
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 
 

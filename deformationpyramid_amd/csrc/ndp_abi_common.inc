@@ -102,7 +102,8 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 //   214: ndp_kpconv_forward_workspace, ndp_kpconv_forward
 //   215: ndp_attention_forward, ndp_feat_conf_workspace, ndp_feat_conf
 //   216: ndp_attention_compat_forward
-extern "C" int ndp_version(void) { return 216; }
+//   217: ndp_attention_forward_lse, ndp_attention_backward
+extern "C" int ndp_version(void) { return 217; }
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }

@@ -1,7 +1,8 @@
 """Lepard's repositioning transformer, coarse matcher, soft-Procrustes layer and pipeline (correspondence/lepard/transformer.py,
 position_encoding.py, matching.py, procrustes.py, pipeline.py) on the HIP operators: the link between kpfcn.KPFCN's coarse descriptors
 and the landmarks that Registration.load_pcds(..., landmarks=) and rigid.reject_landmarks take.  The modules carry the reference's
-parameter names, so the state dict of its `Pipeline` loads with load_state_dict(strict=True).  Forward only.
+parameter names, so the state dict of its `Pipeline` loads with load_state_dict(strict=True).  Inference calls are no_grad;
+GeometryAttentionLayer.forward_grad is the layer recorded for autograd (ops.attention_fn); the rest of the pipeline is forward only.
 
 What runs where: every attention is one ops.attention call (csrc/ndp_attention.inc: the rotary code is applied while q and k are
 staged, the L x S x H scores are never stored); the confidence matrix is ops.feat_conf and the match list ops.feat_match
@@ -16,7 +17,7 @@ confident entries of EACH problem, where the reference takes the batch mean of t
 equal n_b); and torch.topk, like the reference's unstable sort, is free among equal confidences.
 
 Not served: `match_type: sinkhorn` as a confidence matrix (matching.sinkhorn_match gives its match list), `positioning_type:
-randSO3` (a training augmentation), the backward pass.  Parity with a trained Lepard checkpoint is unverified: none is available."""
+randSO3` (a training augmentation), the backward of ops.feat_conf and ops.rigid_fit (so the pipeline as a whole is not trainable).  Parity with a trained Lepard checkpoint is unverified: none is available."""
 import math
 
 import torch
@@ -119,6 +120,14 @@ class GeometryAttentionLayer(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, source, x_pe, source_pe, x_lens=None, source_lens=None):
+        return self._run(ops.attention, x, source, x_pe, source_pe, x_lens, source_lens)
+
+    def forward_grad(self, x, source, x_pe, source_pe, x_lens=None, source_lens=None):
+        """forward's value, recorded for autograd: differentiable in x, source and the layer's parameters (ops.attention_fn)."""
+        with torch.enable_grad():
+            return self._run(ops.attention_fn, x, source, x_pe, source_pe, x_lens, source_lens)
+
+    def _run(self, attention, x, source, x_pe, source_pe, x_lens, source_lens):
         q, k, v = x, source, source
         pe_q = pe_k = None
         if self.pe_type == "sinusoidal":
@@ -126,8 +135,8 @@ class GeometryAttentionLayer(nn.Module):
                 q, k = q + x_pe, k + source_pe
         elif x_pe is not None:
             pe_q, pe_k = x_pe, source_pe
-        o = ops.attention(self.q_proj(q), self.k_proj(k), self.v_proj(v), self.nhead, pe_q=pe_q, pe_k=pe_k,
-                          offsets_q=None if x_lens is None else _offsets(x_lens), offsets_k=None if source_lens is None else _offsets(source_lens))
+        o = attention(self.q_proj(q), self.k_proj(k), self.v_proj(v), self.nhead, pe_q=pe_q, pe_k=pe_k,
+                      offsets_q=None if x_lens is None else _offsets(x_lens), offsets_k=None if source_lens is None else _offsets(source_lens))
         message = self.norm1(self.merge(o))
         message = self.norm2(self.mlp(torch.cat([x, message], dim=1)))
         return x + message

@@ -520,16 +520,10 @@ def feat_conf(fs, ft, temperature=0.1, offsets_s=None, offsets_t=None):
     return conf
 
 
-def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None, pos_q=None, pos_k=None, sigma_spat=None):
-    """Multi-head soft-max attention of stacked, unpadded problems (csrc/ndp_attention.inc: one fused launch, scores and P V on the
-    f32-input MFMA, the L x S x H scores are never stored) -> o [sum L, C].  q [sum L,C], k, v [sum S,C] already projected (made
-    contiguous if they are not); head h owns the channels h D .. h D + D - 1, D = C / n_head.  pe_q [sum L,C,2], pe_k [sum S,C,2]:
-    the (cos, sin) of a rotary code per channel (lepard.VolumetricPositionEncoding), both or neither; q and k are rotated while they
-    are staged, v is not.  scale defaults to D ** -0.5.  offsets_*: B + 1 ascending row offsets for B problems in one call.
-    pos_q [sum L,6], pos_k [sum S,6] float32 and sigma_spat, all three or none: every score is multiplied by the spatial compatibility
-    max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_spat^2) of the rows' (s_xyz, t_xyz) before the scale and the soft-max
-    (ndp_attention_compat_forward, outlier.CorrespondenceAttentionLayer); sigma_spat = inf is the plain call's bits.  Forward only;
-    does not synchronise."""
+def _attention_args(q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat, more=()):
+    """The checks that attention and attention_bwd share -> (q, k, v, pe_q, pe_k, pos_q, pos_k contiguous and checked, C, n_head, scale,
+    sigma_spat, (device offsets, host copy) of either side).  more: (name, tensor, "C" or "H") triples of further tensors that must be
+    [sum L, C] or [sum L, n_head], checked with the shapes, ahead of the device checks."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         if not isinstance(t, torch.Tensor) or t.ndim != 2:
             raise ValueError(f"{name} must be a tensor [rows, C], got {getattr(t, 'shape', type(t))}")
@@ -560,6 +554,10 @@ def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None,
         sigma_spat = float(sigma_spat)
         if not sigma_spat > 0:
             raise ValueError(f"sigma_spat must be positive (inf: no compatibility), got {sigma_spat}")
+    for name, t, width in more:
+        cols = C if width == "C" else n_head
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (q.shape[0], cols):
+            raise ValueError(f"{name} must be [{q.shape[0]}, {cols}], got {getattr(t, 'shape', type(t))}")
     q, k, v = (_chk(t.contiguous() if isinstance(t, torch.Tensor) and t.is_cuda else t, name) for t, name in ((q, "q"), (k, "k"), (v, "v")))
     if pe_q is not None:
         pe_q, pe_k = _chk(pe_q.contiguous() if pe_q.is_cuda else pe_q, "pe_q"), _chk(pe_k.contiguous() if pe_k.is_cuda else pe_k, "pe_k")
@@ -568,9 +566,35 @@ def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None,
     ok, hk = _host_offsets(k.shape[0], offsets_k, "offsets_k", dev)
     if len(hq) != len(hk):
         raise ValueError(f"both sides must list the same problems, got {len(hq) - 1} and {len(hk) - 1}")
-    out = torch.empty_like(q)
     if compat:
         pos_q, pos_k = _chk(pos_q.contiguous() if pos_q.is_cuda else pos_q, "pos_q"), _chk(pos_k.contiguous() if pos_k.is_cuda else pos_k, "pos_k")
+    return q, k, v, pe_q, pe_k, pos_q, pos_k, C, n_head, scale, sigma_spat, (oq, hq), (ok, hk)
+
+
+def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None, pos_q=None, pos_k=None, sigma_spat=None,
+              want_lse=False):
+    """Multi-head soft-max attention of stacked, unpadded problems (csrc/ndp_attention.inc: one fused launch, scores and P V on the
+    f32-input MFMA, the L x S x H scores are never stored) -> o [sum L, C].  q [sum L,C], k, v [sum S,C] already projected (made
+    contiguous if they are not); head h owns the channels h D .. h D + D - 1, D = C / n_head.  pe_q [sum L,C,2], pe_k [sum S,C,2]:
+    the (cos, sin) of a rotary code per channel (lepard.VolumetricPositionEncoding), both or neither; q and k are rotated while they
+    are staged, v is not.  scale defaults to D ** -0.5.  offsets_*: B + 1 ascending row offsets for B problems in one call.
+    pos_q [sum L,6], pos_k [sum S,6] float32 and sigma_spat, all three or none: every score is multiplied by the spatial compatibility
+    max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 / sigma_spat^2) of the rows' (s_xyz, t_xyz) before the scale and the soft-max
+    (ndp_attention_compat_forward, outlier.CorrespondenceAttentionLayer); sigma_spat = inf is the plain call's bits.
+    want_lse: -> (o, lse [sum L, n_head]), the same o and the log-sum-exp of every row's scaled scores (ndp_attention_forward_lse),
+    which attention_bwd takes.  This call itself records nothing for autograd: attention_fn is the differentiable form.  Does not
+    synchronise."""
+    q, k, v, pe_q, pe_k, pos_q, pos_k, C, n_head, scale, sigma_spat, (oq, hq), (ok, hk) = _attention_args(
+        q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat)
+    dev = q.device
+    out = torch.empty_like(q)
+    if want_lse:
+        lse = torch.empty(q.shape[0], n_head, device=dev)
+        N.check(N.lib().ndp_attention_forward_lse(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(pos_q), _p(pos_k), _p(oq), _p(ok), hq, hk,
+                                                  len(hq) - 1, C, n_head, scale, sigma_spat if pos_q is not None else math.inf, _p(out),
+                                                  _p(lse), N.stream_ptr(dev)), "ndp_attention_forward_lse")
+        return out, lse
+    if pos_q is not None:
         N.check(N.lib().ndp_attention_compat_forward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(pos_q), _p(pos_k), _p(oq), _p(ok), hq, hk,
                                                      len(hq) - 1, C, n_head, scale, sigma_spat, _p(out), N.stream_ptr(dev)),
                 "ndp_attention_compat_forward")
@@ -578,6 +602,26 @@ def attention(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None,
     N.check(N.lib().ndp_attention_forward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(oq), _p(ok), hq, hk, len(hq) - 1, C, n_head, scale,
                                           _p(out), N.stream_ptr(dev)), "ndp_attention_forward")
     return out
+
+
+def attention_bwd(q, k, v, o, lse, do, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None, pos_q=None, pos_k=None,
+                  sigma_spat=None):
+    """The gradient of attention's o in the unrotated q, k and v -> (dq [sum L,C], dk [sum S,C], dv [sum S,C]), given do [sum L,C] and
+    the (o, lse) that attention(..., want_lse=True) returned for the same arguments (ndp_attention_backward: two launches that
+    recompute the scores -- no L x S array exists -- fp32 on the f32-input MFMA, no atomics, the same bits run to run).  pe_* and
+    pos_* are data: they get no gradient and the compatibility is not differentiated.  Takes attention's checks; q, k, v, o, lse
+    and do are made contiguous if they are not.  Does not synchronise."""
+    q, k, v, pe_q, pe_k, pos_q, pos_k, C, n_head, scale, sigma_spat, (oq, hq), (ok, hk) = _attention_args(
+        q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat,
+        more=(("o", o, "C"), ("do", do, "C"), ("lse", lse, "H")))
+    o, lse, do = (_chk(t.contiguous() if t.is_cuda else t, name) for t, name in ((o, "o"), (lse, "lse"), (do, "do")))
+    dev = q.device
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(q.shape[0], n_head, device=dev)          # sum_d o do per (row, head): the dq sweep writes it, the dk / dv sweep reads it
+    N.check(N.lib().ndp_attention_backward(_p(q), _p(k), _p(v), _p(pe_q), _p(pe_k), _p(pos_q), _p(pos_k), _p(o), _p(lse), _p(do), _p(oq),
+                                           _p(ok), hq, hk, len(hq) - 1, C, n_head, scale, sigma_spat if pos_q is not None else math.inf,
+                                           _p(delta), _p(dq), _p(dk), _p(dv), N.stream_ptr(dev)), "ndp_attention_backward")
+    return dq, dk, dv
 
 
 RADIUS_MAX_K = 64
@@ -857,6 +901,30 @@ def point_to_plane_distance(x, y, nx, ny, trunc=math.inf, mode=0):
     """-> (total, parts [3] = (x part, y part, normal consistency), idx_x [S] int32).  `total` is differentiable (first derivatives)
     in x and in y; the normals and the nearest-neighbour indices are constants; `parts` are values only."""
     return _PointToPlaneFn.apply(x, y, nx, ny, float(trunc), int(mode))
+
+
+class _AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat):
+        det = lambda t: None if t is None else t.detach()
+        qd, kd, vd = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        ctx.args = dict(n_head=n_head, pe_q=det(pe_q), pe_k=det(pe_k), scale=scale, offsets_q=offsets_q, offsets_k=offsets_k,
+                        pos_q=det(pos_q), pos_k=det(pos_k), sigma_spat=sigma_spat)
+        o, lse = attention(qd, kd, vd, want_lse=True, **ctx.args)
+        ctx.save_for_backward(qd, kd, vd, o, lse)
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        return attention_bwd(q, k, v, o, lse, do.contiguous(), **ctx.args) + (None,) * 9
+
+
+def attention_fn(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=None, offsets_k=None, pos_q=None, pos_k=None, sigma_spat=None):
+    """attention, differentiable (first derivatives) in q, k and v: the forward keeps (q, k, v, o, lse) and the backward is one
+    attention_bwd call.  The codes, the positions and everything else are constants."""
+    return _AttentionFn.apply(q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat)
 
 
 def flow_metrics(flow, flow_gt, overlap=None):

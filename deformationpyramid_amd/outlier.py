@@ -1,7 +1,9 @@
 """The reference's learned outlier filter (correspondence/outlier_rejection/pipeline.py, geometry_attention.py, position_encoding.py,
 loss.py) and its Landmark_Model (correspondence/landmark_estimator.py) on the HIP operators: the link between lepard.Pipeline's
 match list and the landmarks that Registration.load_pcds(..., landmarks=) takes.  The modules carry the reference's parameter
-names, so the state dict of its `Outlier_Rejection` loads with load_state_dict(strict=True).  Forward only.
+names, so the state dict of its `Outlier_Rejection` loads with load_state_dict(strict=True).  forward / confidence are inference
+calls (no_grad); forward_grad / confidence_grad are the same values recorded for autograd on ops.attention_fn, and NeCoLoss,
+synthetic_matches and train_step are what tools/outlier_train.py trains the filter with.
 
 What runs where: every one of the network's layers is one ops.attention call with pos_q = pos_k = vec_6d and sigma_spat
 (csrc/ndp_attention.inc, ndp_attention_compat_forward): the spatial compatibility c[i, j] = max(0, 1 - (|s_i - s_j| - |t_i - t_j|)^2 /
@@ -13,14 +15,15 @@ Problems are UNPADDED, as in lepard.py: vec_6d is the pairs' matches stacked, [s
 that equals the reference's padded batch (_3D_to_6D): a padded row never reaches a valid row's soft-max, LayerNorm or Linear.  A
 pair without matches is left out of the kernel call and gets an empty confidence.
 
-Parity with a trained checkpoint is unverified: none is available."""
+Parity with the reference's own trained checkpoint is unverified: none is available."""
 import copy
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
-from . import lepard, ops
+from . import lepard, ops, synthetic
 from .lepard import _get
 from .matching import _offsets
 
@@ -101,6 +104,14 @@ class CorrespondenceAttentionLayer(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, source, x_pe, source_pe, x_lens=None, source_lens=None, x_pos=None, source_pos=None):
+        return self._run(ops.attention, x, source, x_pe, source_pe, x_lens, source_lens, x_pos, source_pos)
+
+    def forward_grad(self, x, source, x_pe, source_pe, x_lens=None, source_lens=None, x_pos=None, source_pos=None):
+        """forward's value, recorded for autograd: differentiable in x, source and the layer's parameters (ops.attention_fn)."""
+        with torch.enable_grad():
+            return self._run(ops.attention_fn, x, source, x_pe, source_pe, x_lens, source_lens, x_pos, source_pos)
+
+    def _run(self, attention, x, source, x_pe, source_pe, x_lens, source_lens, x_pos, source_pos):
         q, k, v = x, source, source
         pe_q = pe_k = None
         if x_pe is not None:
@@ -113,9 +124,9 @@ class CorrespondenceAttentionLayer(nn.Module):
             if x_pos is None or source_pos is None:
                 raise ValueError("spatial_consistency_check is on: the layer needs the rows' 6-D positions")
             compat = {"pos_q": x_pos, "pos_k": source_pos, "sigma_spat": self.sigma_spat}
-        o = ops.attention(self.q_proj(q), self.k_proj(k), self.v_proj(v), self.nhead, pe_q=pe_q, pe_k=pe_k,
-                          offsets_q=None if x_lens is None else _offsets(x_lens), offsets_k=None if source_lens is None else _offsets(source_lens),
-                          **compat)
+        o = attention(self.q_proj(q), self.k_proj(k), self.v_proj(v), self.nhead, pe_q=pe_q, pe_k=pe_k,
+                      offsets_q=None if x_lens is None else _offsets(x_lens), offsets_k=None if source_lens is None else _offsets(source_lens),
+                      **compat)
         message = self.norm1(self.merge(o))
         message = self.norm2(self.mlp(torch.cat([x, message], dim=1)))
         return x + message
@@ -162,6 +173,14 @@ class Outlier_Rejection(nn.Module):
     @torch.no_grad()
     def confidence(self, vec_6d, lens):
         """vec_6d [sum M_b, 6] stacked with its per-pair lengths (zeros allowed) -> the inlier confidence of every row [sum M_b]."""
+        return self._confidence(vec_6d, lens, False)
+
+    def confidence_grad(self, vec_6d, lens):
+        """confidence's value, recorded for autograd: differentiable in every parameter of the network (training)."""
+        with torch.enable_grad():
+            return self._confidence(vec_6d, lens, True)
+
+    def _confidence(self, vec_6d, lens, grad):
         if vec_6d.shape[0] != sum(lens):
             raise ValueError(f"the lengths {lens} must sum to the {vec_6d.shape[0]} rows of vec_6d")
         if vec_6d.shape[0] == 0:
@@ -171,7 +190,7 @@ class Outlier_Rejection(nn.Module):
         pe_6d = self.positional_encoding(vec_6d)
         feat = self.in_proj(vec_6d)
         for layer in self._6D_geometry_layers:
-            feat = layer(feat, feat, pe_6d, pe_6d, lens, lens, vec_6d, vec_6d)
+            feat = (layer.forward_grad if grad else layer)(feat, feat, pe_6d, pe_6d, lens, lens, vec_6d, vec_6d)
         return self.classification(feat).squeeze(-1)
 
     @torch.no_grad()
@@ -200,6 +219,78 @@ def compute_inlier_mask(data, inlier_thr, s2t_flow, rot, trn):
         masks.append(inlier)
         rates.append(inlier.sum().float() / n if n else inlier.new_tensor(float("nan"), dtype=torch.float32))
     return masks, rates
+
+
+class NeCoLoss(nn.Module):
+    """loss.py's NeCoLoss on the stacked layout.  forward(data) takes what Outlier_Rejection.forward left in data (vec_6d,
+    vec_6d_lengths, vec_6d_ind; inlier_conf [sum M_b] -- from confidence_grad when the loss is to be differentiated) and the ground
+    truth: coarse_flow, a list of [S_b, 3] flows on the pairs' coarse source points, batched_rot [B, 3, 3], batched_trn [B, 3, 1]
+    -> {"loss", "IR Lepard", "IR NeCo"}: the class-weighted BCE against compute_inlier_mask's labels, the matcher's inlier rate
+    and the inlier rate of the matches with confidence above 0.5 (the mean over the pairs that keep any; 0 when none does)."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.inlier_thr = _get(config, "inlier_thr")
+        self.mutual_nearest, self.dataset, self.balanced = (_get(config, key) for key in ("mutual_nearest", "dataset", "balanced_bce"))
+
+    def forward(self, data):
+        masks, rates = compute_inlier_mask(data, self.inlier_thr, torch.cat(list(data["coarse_flow"])), data["batched_rot"], data["batched_trn"])
+        info = {"IR Lepard": torch.stack(rates).mean()}
+        conf = data["inlier_conf"].reshape(-1)
+        loss = self.get_weighted_bce_loss(conf, torch.cat(masks).float())
+        off = _offsets(data["vec_6d_lengths"])
+        ir = []
+        for b, mask in enumerate(masks):
+            kept = mask[conf[off[b]:off[b + 1]] > 0.5]
+            if kept.shape[0] > 0:
+                ir.append(kept.sum() / kept.shape[0])
+        info["IR NeCo"] = torch.stack(ir).mean() if ir else 0
+        info["loss"] = loss
+        return info
+
+    @staticmethod
+    def get_weighted_bce_loss(prediction, gt):
+        """The reference's weighting, as written: an inlier weighs the outliers' share of the labels, an outlier the inliers', and
+        the weighted terms are averaged over all rows."""
+        class_loss = nn.functional.binary_cross_entropy(prediction, gt, reduction="none")
+        weights = torch.ones_like(gt)
+        w_negative = gt.sum() / gt.size(0)
+        w_positive = 1 - w_negative
+        weights[gt >= 0.5] = w_positive
+        weights[gt < 0.5] = w_negative
+        return torch.mean(weights * class_loss)
+
+
+def synthetic_matches(n_inlier, n_outlier, seed, device="cpu"):
+    """A seeded pair's putative matches -> (vec_6d [M, 6] float32, labels [M] bool), M = n_inlier + n_outlier.  The source ends
+    are samples of synthetic.surface_pair's star-shaped surface (synthetic.surface_radius); an inlier's target end is its own image
+    under that pair's motion (synthetic.surface_deform, then the rotation by SURFACE_ROT_Z about z and the translation SURFACE_TRN),
+    an outlier's the image of another, uniformly drawn sample; the rows are shuffled.  Drawn with numpy's seeded MT19937 and computed
+    in float64 on the host, so the batch is the same on every machine."""
+    rs = np.random.RandomState(seed)
+    M = n_inlier + n_outlier
+    d = rs.standard_normal((M, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    ph = rs.uniform(0.0, 2.0 * math.pi, 4)
+    src = d * synthetic.surface_radius(d, ph, np)[:, None]
+    c, s = math.cos(synthetic.SURFACE_ROT_Z), math.sin(synthetic.SURFACE_ROT_Z)
+    Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    image = synthetic.surface_deform(src, ph[3], np) @ Rz.T + np.array(synthetic.SURFACE_TRN)
+    wrong = (np.arange(M) + rs.randint(1, M, size=M)) % M if M > 1 else np.zeros(M, np.int64)     # never the row itself
+    labels = np.arange(M) < n_inlier
+    tgt = np.where(labels[:, None], image, image[wrong])
+    order = rs.permutation(M)
+    vec_6d = np.concatenate([src, tgt], 1)[order].astype(np.float32)
+    return torch.from_numpy(vec_6d).to(device), torch.from_numpy(labels[order]).to(device)
+
+
+def train_step(model, optimizer, vec_6d, lens, labels):
+    """One optimiser step of the filter on stacked matches with their inlier labels [sum M_b] bool -> the loss before the step."""
+    optimizer.zero_grad(set_to_none=True)
+    loss = NeCoLoss.get_weighted_bce_loss(model.confidence_grad(vec_6d, lens), labels.float())
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
 
 
 @torch.no_grad()

@@ -29,6 +29,21 @@ def synthetic_pair(p, n_total=16384, partial=True):
     return src, tgt, flow_gt, overlap
 
 
+# surface_pair's surface and motion, shared with outlier.synthetic_matches (which draws with numpy: xp = numpy there)
+SURFACE_ROT_Z, SURFACE_TRN = 0.25, (0.08, -0.03, 0.05)
+
+
+def surface_radius(d, ph, xp=torch):
+    """The star-shaped surface: the radius along the unit directions d [n, 3] at the phases ph [>= 3]."""
+    return 0.35 * (1.0 + 0.18 * xp.sin(3.0 * d[:, 0] + ph[0]) * xp.sin(2.0 * d[:, 1] + ph[1])
+                   + 0.10 * xp.cos(4.0 * d[:, 2] + ph[2]))
+
+
+def surface_deform(x, a, xp=torch):
+    """The pair's deformation phi(x) = x + 0.05 sin(2.5 x + a)."""
+    return x + 0.05 * xp.sin(2.5 * x + a)
+
+
 def surface_pair(p, n_total=16384, partial=True):
     """Seeded pair of SURFACE samples (what 4DMatch scans are): a star-shaped bumpy closed surface, sampled twice (source /
     target base: no exact correspondences), target deformed by phi(q) = q + 0.05 sin(2.5 q + a_p), rotated about z by
@@ -38,16 +53,14 @@ def surface_pair(p, n_total=16384, partial=True):
     d = torch.randn(n_total, 3, generator=g, dtype=torch.float32)
     d = d / d.norm(dim=1, keepdim=True)
     ph = torch.rand(4, generator=g, dtype=torch.float32) * 6.2831853
-    r = 0.35 * (1.0 + 0.18 * torch.sin(3.0 * d[:, 0] + ph[0]) * torch.sin(2.0 * d[:, 1] + ph[1])
-                + 0.10 * torch.cos(4.0 * d[:, 2] + ph[2]))
-    q = d * r[:, None]
+    q = d * surface_radius(d, ph)[:, None]
     src, tgt_base = q[0::2].contiguous(), q[1::2].contiguous()
-    c, s = float(math.cos(0.25)), float(math.sin(0.25))
+    c, s = float(math.cos(SURFACE_ROT_Z)), float(math.sin(SURFACE_ROT_Z))
     Rz = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32)
-    t = torch.tensor([0.08, -0.03, 0.05], dtype=torch.float32)
+    t = torch.tensor(SURFACE_TRN, dtype=torch.float32)
 
     def phi(x):
-        return x + 0.05 * torch.sin(2.5 * x + ph[3])
+        return surface_deform(x, ph[3])
 
     tgt = phi(tgt_base) @ Rz.T + t
     flow_gt = phi(src) @ Rz.T + t - src

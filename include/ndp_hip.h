@@ -446,7 +446,7 @@ int ndp_kpconv_forward(const float *q, const float *s, const int *idx, const flo
  *   One launch; scores and P V on the f32-input MFMA (exact fp32 products, one rounding per term), an online soft-max over key
  *   tiles in ascending order, every partial result folded in one fixed order, no atomics.  No bit of an output row depends on the
  *   other problems of the call, on the other query rows, or on where the row falls in its block.  Nothing is data-dependent: the
- *   entry DOES NOT synchronise.  No backward pass.
+ *   entry DOES NOT synchronise.  The backward pass: ndp_attention_backward below (ABI 217).
  *   NDP_E_UNSUPPORTED: outside 1 <= C <= 1056, 1 <= n_head <= 16 with C % n_head == 0 and C / n_head <= 264, rows <= 2^30 a side.
  *   NDP_E_INVALID: B outside 1..65535, bad offsets (negative, not monotone, an empty side), a NULL or misaligned pointer, one of
  *   pe_q / pe_k without the other, a rotary code with an odd C / n_head, a scale that is not finite.
@@ -474,6 +474,30 @@ int ndp_attention_forward(const float *q, const float *k, const float *v, const 
 int ndp_attention_compat_forward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k,
                                  const float *pos_q, const float *pos_k, const int *offQ, const int *offK, const int *offQ_host,
                                  const int *offK_host, int B, int C, int n_head, float scale, double sigma_spat, float *o, void *stream);
+/* Attention with statistics and the attention backward (ABI 217; DESIGN.md "Attention backward"): what training on the two entries
+ * above needs.  pos_q / pos_k are both given (the compatibility-modulated form, sigma_spat as ndp_attention_compat_forward's) or
+ * both NULL (the plain form; sigma_spat is not read).  sigma_spat = +inf is the plain form's bits.
+ * ndp_attention_forward_lse: o as ndp_attention_forward / ndp_attention_compat_forward write it, bit for bit, and
+ *   lse [sum L][n_head], lse[i, h] = log sum_j exp(score[i, j, h]), the log-sum-exp of the row's scaled (and modulated) scores.
+ * ndp_attention_backward: given do [sum L][C] and the o, lse of ndp_attention_forward_lse for the same arguments,
+ *     dq [sum L][C], dk, dv [sum S][C]: the gradient of sum(o * do) in the UNROTATED q, k and v.
+ *   pe_* and pos_* are data: they get no gradient and c is not differentiated.  Two launches that recompute the scores tile by tile
+ *   (no L x S array in global memory): the dq sweep (16 query rows a workgroup, key tiles in ascending order; it also writes
+ *   delta[i, h] = sum_d o do) and the dk / dv sweep (16 key rows a workgroup, query tiles in ascending order).  A walked tile has 64
+ *   rows for C / n_head <= 144 and 48 above, so that the LDS of a workgroup fits 160 KiB at C / n_head = 264.  fp32 on the f32-input
+ *   MFMA, no atomics, one writer per output element, every sum in one fixed order: the same bits run to run.  A key with c = 0 takes
+ *   part in the soft-max, so it feeds dv and delta, and feeds nothing to dq or dk.  The rotation is undone while a block is written:
+ *   no rotated copy reaches global memory.  No bit of a row of dq depends on the other query rows, and none of any output on the
+ *   other problems of the call.  delta [sum L][n_head] floats is the call's workspace.  Neither entry synchronises.
+ *   Refused as ndp_attention_forward, and NDP_E_INVALID: a NULL or misaligned o, lse, do, delta, dq, dk or dv, one of pos_q / pos_k
+ *   without the other, and with positions a sigma_spat that ndp_attention_compat_forward refuses.                                  */
+int ndp_attention_forward_lse(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const float *pos_q,
+                              const float *pos_k, const int *offQ, const int *offK, const int *offQ_host, const int *offK_host, int B,
+                              int C, int n_head, float scale, double sigma_spat, float *o, float *lse, void *stream);
+int ndp_attention_backward(const float *q, const float *k, const float *v, const float *pe_q, const float *pe_k, const float *pos_q,
+                           const float *pos_k, const float *o, const float *lse, const float *dout, const int *offQ, const int *offK,
+                           const int *offQ_host, const int *offK_host, int B, int C, int n_head, float scale, double sigma_spat,
+                           float *delta, float *dq, float *dk, float *dv, void *stream);
 int ndp_feat_conf_workspace(int B, long long nS, long long nT, long long *nbytes);
 int ndp_feat_conf(const float *fs, const float *ft, const int *offS, const int *offT, const int *offS_host, const int *offT_host,
                   int B, int C, float temperature, void *ws, float *conf, int Smax, int Tmax, void *stream);

@@ -1,7 +1,7 @@
 // ------------------------------------------------------------------------------------------------
 // Exact nearest neighbours by a grid ball search (engine flag nn_cells; ndp_chamfer_nn_cells).
 //   The dense kernels evaluate all S x T distances every tick although the answer changes for a few percent of the queries from
-//   one tick to the next.  Here the references of a direction are sorted into a uniform grid of NNC_NG^3 cells; a query takes the
+//   one tick to the next.  Here the references of a direction are sorted into a uniform grid of NNC_NGX x NNC_NGY x NNC_NGZ cells; a query takes the
 //   EXACT distance to a seed reference (last tick's neighbour) as the radius of a ball, evaluates only the references in the cells
 //   that the ball's bounding box touches and keeps the lexicographic minimum of (d2, index) -- the minimum distance with the lowest
 //   index among equals, which is what k_nn reports.  Every distance is nn_exact_d2, the brute force's own fma chain, and the minimum
@@ -9,8 +9,9 @@
 //   atomics) and no float atomic is used.
 //
 //   Geometry (per pair, from the TARGETS' bounding box, fixed while the pair lives in its slot): origin o = the box's minimum,
-//   inv_h = NNC_NG / extent per axis -- 0 where the extent is 0 or the quotient is not finite, which puts the whole axis into cell 0.
-//       cell(p) = (int) min(max(floor((p - o) * inv_h), 0), NNC_NG - 1)                                              (nnc_cell1)
+//   inv_h = NG_a / extent per axis a, NG_a that axis' cell count -- 0 where the extent is 0 or the quotient is not finite, which puts the
+//   whole axis into cell 0.
+//       cell(p) = (int) min(max(floor((p - o) * inv_h), 0), NG_a - 1)                                                (nnc_cell1)
 //   per axis, the SAME float expression for references and for the bounds of a query.  It is MONOTONE in p: a rounded subtraction, a
 //   rounded product with a non-negative factor, floor and the clamp are each non-decreasing (a NaN goes to cell 0 in every case:
 //   max(NaN, 0) = 0).  Points outside the box -- the warped sources, which are sorted into the targets' geometry -- fall into
@@ -29,23 +30,52 @@
 //        cell(fl(q_a - r')) <= cell(t_a) <= cell(fl(q_a + r')) whatever its roundings are.
 //   Hence every reference at chain distance <= b2 lies in the enumerated cells, whatever the seed: correctness never rests on
 //   coherence between ticks; a poor seed only costs candidates.  A bound that is not finite (inf or NaN) enumerates the whole grid.
+//   The argument is per axis and never compares two axes: it holds for any cell count per axis.
+//
+//   CELLS PER AXIS.  The records of a cell row (fixed y and z cell, x cells lo .. hi) lie contiguously, so a box costs one ROW step per
+//   (y, z) cell -- two cell_start reads, the address arithmetic, a loop set-up -- and one RECORD step per record.  The lanes of a wave
+//   walk in lock step: a wave issues, per row iteration, as many record steps as its busiest lane has records in that row.  At config A
+//   the ball's radius is about one cell of a 16^3 grid; 64 x 8 x 8 cells (x, the row axis, fine; y and z coarse) halve the rows of a box
+//   (5.3 -> 2.6 per query) for a third more records (8.4 -> 11.4), and the modelled steps of a wave (tools/nn_wave_steps.py over the
+//   oracle's own trajectories, profiles/nn_wave_steps.txt) fall from 70.7 to 61.0, a row step costing about 1.4 record steps on top.
+//   Measured (profiles/nn_loss_tick_ab.txt): 16^3 0.048 ms, 32 x 16 x 8 0.042, 64 x 8 x 8 0.041, 64 x 16 x 4 0.044, 128 x 8 x 4 0.048,
+//   256 x 4 x 4 0.059.  The wide search (ndp_nn_cells_wide.inc) keeps 16^3 (NNC_NG): the functions below take the counts as template
+//   parameters.
+//
+//   THE MINIMUM AS ONE KEY.  A chain distance is +0, positive, +inf or NaN (squares and sums of squares: never -0, never negative), so
+//   its bit pattern orders as its value does, and (d2, index) is kept as the unsigned 64-bit key d2-bits : index with ONE compare and
+//   two selects per record (eleven vector instructions per record step; the record is {index, x, y, z} so that the loaded index and the
+//   distance computed over x form the key's register pair without a move).  The three corners come out as with two compares:
+//     * a NaN distance never wins: its bits (0x7f800001 .. 0x7fffffff, or with the sign bit set) are ABOVE +inf's, and the running key
+//       starts at (+inf, 0) and is replaced only by a strictly smaller one;
+//     * d2 = +inf leaves index -1: a key (+inf, j) is not strictly below the start (+inf, 0) for any j >= 0, so the start survives, and a
+//       final key whose distance is +inf reports index -1 (no finite distance was seen);
+//     * equal distances take the lowest index: the index is the key's low word.
 //
 //   SEEDS.  The seed is last tick's index of the query when there is one: not on a pair's first evaluation (total_evals == 0: the
 //   slot's index buffers survive a refill and belong to ANOTHER pair), and not where it is negative or >= the reference count
 //   (a stale index of a larger pair).  A stale index IN range is a valid seed like any other.  Without a seed the bound comes from
-//   the grid: the smallest chain distance to the records of the nearest non-empty cells, found by growing a Chebyshev cube around the
-//   query's own (clamped) cell until it holds a record.
+//   the grid: the smallest chain distance to the records of the nearest non-empty cells, found by growing a Chebyshev cube -- a cube in
+//   space: an axis with more cells takes proportionally more of them per step -- around the query's own (clamped) cell until it holds a
+//   record.  ANY record's chain distance is a valid bound, so the region's shape is a matter of cost only.
 //
 //   Launch: one 1024-thread workgroup per pair and DIRECTION (blockIdx.x: 0 sources -> targets, 1 targets -> sources), each thread up
 //   to two queries: the stage lasts as long as ONE workgroup (512 of them on 256 CUs), so a workgroup's own chain is what counts.
-//   Measured at 256 pairs (profiles/nn_cells_variants.txt): 512 threads x four queries 0.076 ms, 1024 x two 0.060 ms.  The walk is bound
+//   Measured at 256 pairs on the 16^3 grid with two compares per record (profiles/nn_cells_variants.txt): 512 threads x four queries
+//   0.076 ms, 1024 x two 0.060 ms.  The walk is bound
 //   by the NUMBER of record reads and evaluations a wave issues -- as many as its busiest lane needs -- not by their latency: reading
 //   2 / 4 / 8 records of a cell row together (the surplus re-reads the last one) measured 0.065 / 0.073 / 0.102 ms and was not kept; nor
 //   were queries taken in cell order (0.060) or a first look into the query's own cell to tighten a stale seed's bound (0.062).
 //   LDS per workgroup: records 32 KB + cell_start 16 KB.  Scope: S, T <= NNC_MAX (configs A and B); up to 8192: ndp_nn_cells_wide.inc.
 // ------------------------------------------------------------------------------------------------
-#define NNC_NG 16
-#define NNC_NC (NNC_NG * NNC_NG * NNC_NG)
+#ifndef NNC_NGX                                /* cells per axis of this file's search (x: the axis a row runs along) */
+#define NNC_NGX 64
+#define NNC_NGY 8
+#define NNC_NGZ 8
+#endif
+#define NNC_NG 16                             /* cells per axis of the wide search (ndp_nn_cells_wide.inc): 16^3 */
+#define NNC_NC 4096                           /* cells of either grid: the cell_start table is 16 KB */
+static_assert(NNC_NGX * NNC_NGY * NNC_NGZ == NNC_NC && NNC_NG * NNC_NG * NNC_NG == NNC_NC, "both grids fill the same cell_start table");
 #define NNC_MAX 2048                          /* references / queries per cloud */
 #define NNC_NT 1024
 #define NNC_NW (NNC_NT / 64)
@@ -58,8 +88,18 @@ __host__ __device__ inline bool nnc_fits(int n_cap, int t_cap) { return n_cap >=
 
 struct NncGeom { float o[3], ih[3]; };
 
-__device__ __forceinline__ int nnc_cell1(float p, float o, float ih) {
-    return (int)fminf(fmaxf(floorf((p - o) * ih), 0.f), (float)(NNC_NG - 1));
+__device__ __forceinline__ int nnc_cell1(float p, float o, float ih, int ng) {
+    return (int)fminf(fmaxf(floorf((p - o) * ih), 0.f), (float)(ng - 1));
+}
+// the cell of a point, x fastest
+template <int GX, int GY, int GZ>
+__device__ __forceinline__ int nnc_cell3(const float (&v)[3], const NncGeom &g) {
+    return (nnc_cell1(v[2], g.o[2], g.ih[2], GZ) * GY + nnc_cell1(v[1], g.o[1], g.ih[1], GY)) * GX + nnc_cell1(v[0], g.o[0], g.ih[0], GX);
+}
+// inv_h of an axis of ng cells and the given extent: 0 for a zero (or vanishing) extent -- one cell on this axis
+__device__ __forceinline__ float nnc_inv_h(float ext, int ng) {
+    const float ih = ext > 0.f ? (float)ng / ext : 0.f;
+    return ih < INFINITY ? ih : 0.f;
 }
 __device__ __forceinline__ NncGeom nnc_load_geom(const float *g) {
     NncGeom r;
@@ -86,7 +126,7 @@ __device__ __forceinline__ int nnc_block_excl_scan(int v, int *tmp, int t) {
     return base + inc - v;
 }
 
-// Counting sort of n <= NNC_MAX points [n][3] into the grid: rec[k] = {x, y, z, index} grouped by cell (x fastest), cs[c] .. cs[c + 1]
+// Counting sort of n <= NNC_MAX points [n][3] into the grid: rec[k] = {index, x, y, z} grouped by cell (x fastest), cs[c] .. cs[c + 1]
 // the records of cell c.  In place: cs[c + 1] counts, then holds the cell's first slot, and the scatter's own cursor moves it to the
 // cell's end -- which is the next cell's first slot.  All NNC_NT threads call this.
 __device__ __forceinline__ void nnc_build_lds(const float *pts, int n, const NncGeom &g, float4 *rec, int *cs, int *tmp, int t) {
@@ -98,7 +138,7 @@ __device__ __forceinline__ void nnc_build_lds(const float *pts, int n, const Nnc
         const int i = t + NNC_NT * u;
         const float *rp = pts + 3 * (size_t)(i < n ? i : 0);
         v[u][0] = rp[0]; v[u][1] = rp[1]; v[u][2] = rp[2];
-        cell[u] = (nnc_cell1(v[u][2], g.o[2], g.ih[2]) * NNC_NG + nnc_cell1(v[u][1], g.o[1], g.ih[1])) * NNC_NG + nnc_cell1(v[u][0], g.o[0], g.ih[0]);
+        cell[u] = nnc_cell3<NNC_NGX, NNC_NGY, NNC_NGZ>(v[u], g);
     }
     __syncthreads();
 #pragma unroll
@@ -118,54 +158,70 @@ __device__ __forceinline__ void nnc_build_lds(const float *pts, int n, const Nnc
         const int i = t + NNC_NT * u;
         if (i < n) {
             const int pos = atomicAdd(&cs[cell[u] + 1], 1);
-            rec[pos] = make_float4(v[u][0], v[u][1], v[u][2], __int_as_float(i));
+            rec[pos] = make_float4(__int_as_float(i), v[u][0], v[u][1], v[u][2]);
         }
     }
     __syncthreads();
 }
 
-// lexicographic minimum of (d2, index) over the records of the cells [lo, hi] (per axis, inclusive); returns whether a record was seen
+// lexicographic minimum of (d2, index) over the records of the cells [lo, hi] (per axis, inclusive) of a GX x GY x . grid, from
+// (+inf, -1); returns whether a record was seen.  The minimum is kept as ONE unsigned key, d2's bits above the index (see the header).
+template <int GX, int GY>
 __device__ __forceinline__ bool nnc_scan_box(const float4 *rec, const int *cs, const float (&q)[3], const int (&lo)[3], const int (&hi)[3],
                                              float &bd, int &bj) {
     bool seen = false;
+    unsigned long long best = (unsigned long long)0x7f800000u << 32;           // (+inf, 0): no record with d2 = +inf or NaN is below it
     const int ny = hi[1] - lo[1] + 1, nrow = ny * (hi[2] - lo[2] + 1);
-    int cy = lo[1], cz = lo[2];
-    int row = (cz * NNC_NG + cy) * NNC_NG;
-    int k0 = cs[row + lo[0]], k1 = cs[row + hi[0] + 1];
+    // a row's segment is cs[c0] .. cs[c0 + w]; c0 moves by GX from row to row and by zstep more where y wraps
+    const int w = hi[0] - lo[0] + 1, zstep = (GY - ny) * GX;
+    int c0 = (lo[2] * GY + lo[1]) * GX + lo[0], left = ny;
+    int k0 = cs[c0], k1 = cs[c0 + w];
     for (int r = 0; r < nrow; ++r) {
         // the next row's segment is requested before this row's records are walked (a chain of dependent LDS round trips otherwise)
         int n0 = 0, n1 = 0;
         if (r + 1 < nrow) {
-            if (++cy > hi[1]) { cy = lo[1]; ++cz; }
-            row = (cz * NNC_NG + cy) * NNC_NG;
-            n0 = cs[row + lo[0]]; n1 = cs[row + hi[0] + 1];
+            c0 += GX;
+            if (--left == 0) { left = ny; c0 += zstep; }
+            n0 = cs[c0]; n1 = cs[c0 + w];
         }
         seen |= k1 > k0;
-        for (int k = k0; k < k1; ++k) {
-            const float4 c = rec[k];
-            const float d = nn_exact_d2(q[0], q[1], q[2], c.x, c.y, c.z);
-            const int j = __float_as_int(c.w);
-            if (d < bd || (d == bd && j < bj)) { bd = d; bj = j; }
+        for (const float4 *p = rec + k0, *pe = rec + k1; p < pe; ++p) {     // (one cursor: no record index to step beside the address)
+            const float4 c = *p;
+            const float d = nn_exact_d2(q[0], q[1], q[2], c.y, c.z, c.w);
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | __float_as_uint(c.x);
+            best = key < best ? key : best;
         }
         k0 = n0; k1 = n1;
     }
+    bd = __uint_as_float((unsigned)(best >> 32));
+    bj = (best >> 32) == 0x7f800000u ? -1 : (int)(unsigned)best;
     return seen;
 }
 
 // One query against the grid in LDS.  b2: the chain distance to the seed, or a negative value when there is no seed.
+template <int GX, int GY, int GZ>
 __device__ __forceinline__ void nnc_query(const float4 *rec, const int *cs, const NncGeom &g, const float (&q)[3], float b2, float &bd, int &bj) {
+    constexpr int ng[3] = {GX, GY, GZ};
+    // The growing region of a query without a seed is a cube IN SPACE, not in cells: an axis with sc times the cells of the coarsest axis
+    // takes sc cells per step (and sc / 2 at step 0), so that the first record found is near in every direction and the ball it bounds stays
+    // small.  (In cells -- one per step on every axis -- a 64 x 8 x 8 grid found its first record up to a coarse cell away in y or z and
+    // walked a ball of that radius: 13 fine cells either way in x.)  Step gmin reaches every cell of every axis.
+    constexpr int gmin = GX < GY ? (GX < GZ ? GX : GZ) : (GY < GZ ? GY : GZ);
+    constexpr int sc[3] = {GX / gmin, GY / gmin, GZ / gmin};
+    static_assert(sc[0] * gmin == GX && sc[1] * gmin == GY && sc[2] * gmin == GZ, "cells per axis: multiples of the coarsest axis' count");
     int lo[3], hi[3];
     if (b2 < 0.f) {                                   // no seed: the nearest non-empty cells give the bound
         int c[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) c[a] = nnc_cell1(q[a], g.o[a], g.ih[a]);
+        for (int a = 0; a < 3; ++a) c[a] = nnc_cell1(q[a], g.o[a], g.ih[a], ng[a]);
         b2 = INFINITY;
-        for (int r = 0; r < NNC_NG; ++r) {
+#pragma unroll 1                                       // (nine copies of the scan tripled the kernel's code: 0.039 -> 0.044 ms at 256 pairs)
+        for (int r = 0; r <= gmin; ++r) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) { lo[a] = max(c[a] - r, 0); hi[a] = min(c[a] + r, NNC_NG - 1); }
-            float sd = INFINITY;
-            int sj = -1;
-            if (nnc_scan_box(rec, cs, q, lo, hi, sd, sj)) { b2 = sd; break; }
+            for (int a = 0; a < 3; ++a) { lo[a] = max(c[a] - r * sc[a] - sc[a] / 2, 0); hi[a] = min(c[a] + r * sc[a] + sc[a] / 2, ng[a] - 1); }
+            float sd;
+            int sj;
+            if (nnc_scan_box<GX, GY>(rec, cs, q, lo, hi, sd, sj)) { b2 = sd; break; }
         }
     }
     if (b2 < INFINITY) {
@@ -173,15 +229,14 @@ __device__ __forceinline__ void nnc_query(const float4 *rec, const int *cs, cons
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const float r = rs + fabsf(q[a]) * 0x1p-20f;
-            lo[a] = nnc_cell1(q[a] - r, g.o[a], g.ih[a]);
-            hi[a] = nnc_cell1(q[a] + r, g.o[a], g.ih[a]);
+            lo[a] = nnc_cell1(q[a] - r, g.o[a], g.ih[a], ng[a]);
+            hi[a] = nnc_cell1(q[a] + r, g.o[a], g.ih[a], ng[a]);
         }
     } else {                                          // inf or NaN: the whole grid
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = 0; hi[a] = NNC_NG - 1; }
+        for (int a = 0; a < 3; ++a) { lo[a] = 0; hi[a] = ng[a] - 1; }
     }
-    bd = INFINITY; bj = -1;
-    nnc_scan_box(rec, cs, q, lo, hi, bd, bj);
+    nnc_scan_box<GX, GY>(rec, cs, q, lo, hi, bd, bj);
 }
 
 // One direction of one pair: queries qs [nq][3] against references rs [nr][3] (both <= NNC_MAX).
@@ -221,7 +276,7 @@ __device__ __forceinline__ void nnc_body(const float *qs, int nq, const float *r
         if (i < nq) {
             float bd;
             int bj;
-            nnc_query(rec, cs, g, q[u], b2[u], bd, bj);
+            nnc_query<NNC_NGX, NNC_NGY, NNC_NGZ>(rec, cs, g, q[u], b2[u], bd, bj);
             d2[i] = bd; idx[i] = bj;
         } else if (i < pad_to) idx[i] = -1;
     }
@@ -249,9 +304,7 @@ __device__ __forceinline__ void nnc_build_global(const float *ys, int T, float *
 #pragma unroll
         for (int w = 1; w < NNC_NW; ++w) { lo = fminf(lo, red[w]); hi = fmaxf(hi, red[NNC_NW + w]); }
         __syncthreads();
-        const float ext = hi - lo;
-        float ih = ext > 0.f ? (float)NNC_NG / ext : 0.f;
-        if (!(ih < INFINITY)) ih = 0.f;                        // a zero (or vanishing) extent: one cell on this axis
+        const float ih = nnc_inv_h(hi - lo, a == 0 ? NNC_NGX : a == 1 ? NNC_NGY : NNC_NGZ);
         g.o[a] = lo; g.ih[a] = ih;
         if (t == 0) { geom[a] = lo; geom[3 + a] = ih; }
     }

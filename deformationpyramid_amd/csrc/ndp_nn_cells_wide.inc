@@ -2,7 +2,8 @@
 // The exact grid ball search for clouds of up to NNW_MAX = 8192 points (engine flag nn_cells_wide; ndp_chamfer_nn_cells_wide).
 //   Same algorithm, same geometry and same exactness argument as ndp_nn_cells.inc (its header's WHY THE RANGE IS CONSERVATIVE and SEEDS
 //   hold here word for word): per query the radius is the chain distance nn_exact_d2 to a seed, every cell the ball's bounding box touches
-//   is enumerated (nnc_query / nnc_scan_box / nnc_cell1 are that file's own functions, called unchanged) and the result is the
+//   is enumerated (nnc_query / nnc_scan_box / nnc_cell1 are that file's own functions, called with NNC_NG = 16 cells on every axis -- the
+//   per-axis counts of the 2048-point search were chosen for ITS ball sizes and are not measured here) and the result is the
 //   lexicographic minimum of (d2, index) -- the brute force's bits for ANY seed values.  What differs is the kernels' shape:
 //
 //   * A reference grid of 8192 records is 128 KB of LDS, so a workgroup holds ONE grid and nothing else of that size: the grids are sorted
@@ -30,7 +31,7 @@
 __host__ __device__ inline bool nnw_fits(int n_cap, int t_cap) { return n_cap >= 1 && t_cap >= 1 && n_cap <= NNW_MAX && t_cap <= NNW_MAX; }
 __host__ __device__ inline int nnw_chunks(int n_cap, int t_cap) { return ((n_cap > t_cap ? n_cap : t_cap) + NNW_CH - 1) / NNW_CH; }
 
-// Counting sort of n <= NNW_MAX points [n][3] into the grid g: grec[k] = {x, y, z, index} grouped by cell in GLOBAL memory, gcs[0 .. NNC_CS)
+// Counting sort of n <= NNW_MAX points [n][3] into the grid g: grec[k] = {index, x, y, z} grouped by cell in GLOBAL memory, gcs[0 .. NNC_CS)
 // the cell_start table there.  The counters live in LDS (cs: NNC_CS ints, tmp: 2 NNC_NW ints) exactly as in nnc_build_lds.  All NNW_NT threads.
 __device__ __forceinline__ void nnw_sort_global(const float *pts, int n, const NncGeom &g, float4 *grec, int *gcs, int *cs, int *tmp, int t) {
     for (int c = t; c < NNC_NC + 1; c += NNW_NT) cs[c] = 0;
@@ -41,7 +42,7 @@ __device__ __forceinline__ void nnw_sort_global(const float *pts, int n, const N
         const int i = t + NNW_NT * u;
         const float *rp = pts + 3 * (size_t)(i < n ? i : 0);
         v[u][0] = rp[0]; v[u][1] = rp[1]; v[u][2] = rp[2];
-        cell[u] = (nnc_cell1(v[u][2], g.o[2], g.ih[2]) * NNC_NG + nnc_cell1(v[u][1], g.o[1], g.ih[1])) * NNC_NG + nnc_cell1(v[u][0], g.o[0], g.ih[0]);
+        cell[u] = nnc_cell3<NNC_NG, NNC_NG, NNC_NG>(v[u], g);
     }
     __syncthreads();
 #pragma unroll
@@ -64,7 +65,7 @@ __device__ __forceinline__ void nnw_sort_global(const float *pts, int n, const N
         const int i = t + NNW_NT * u;
         if (i < n) {
             const int pos = atomicAdd(&cs[cell[u] + 1], 1);
-            grec[pos] = make_float4(v[u][0], v[u][1], v[u][2], __int_as_float(i));
+            grec[pos] = make_float4(__int_as_float(i), v[u][0], v[u][1], v[u][2]);
         }
     }
 }
@@ -90,9 +91,7 @@ __device__ __forceinline__ void nnw_build_global(const float *ys, int T, float *
 #pragma unroll
         for (int w = 1; w < NNC_NW; ++w) { lo = fminf(lo, red[w]); hi = fmaxf(hi, red[NNC_NW + w]); }
         __syncthreads();
-        const float ext = hi - lo;
-        float ih = ext > 0.f ? (float)NNC_NG / ext : 0.f;
-        if (!(ih < INFINITY)) ih = 0.f;                        // a zero (or vanishing) extent: one cell on this axis
+        const float ih = nnc_inv_h(hi - lo, NNC_NG);
         g.o[a] = lo; g.ih[a] = ih;
         if (t == 0) { geom[a] = lo; geom[3 + a] = ih; }
     }
@@ -134,7 +133,7 @@ __device__ __forceinline__ void nnw_body(const float *qs, int nq, const float *r
         if (i < nq) {
             float bd;
             int bj;
-            nnc_query(rec, cs, g, q[u], b2[u], bd, bj);
+            nnc_query<NNC_NG, NNC_NG, NNC_NG>(rec, cs, g, q[u], b2[u], bd, bj);
             d2[i] = bd; idx[i] = bj;
         } else if (i < pad_to) idx[i] = -1;
     }

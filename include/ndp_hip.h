@@ -213,7 +213,7 @@ int ndp_engine_nn_matrix_fits(int n_cap);
 int ndp_engine_nn_onepass_fits(int n_cap);
 
 /* The same result from an exact grid ball search (what an engine with nn_cells runs every tick): the references of each direction are
- * sorted into a 16^3 grid over the TARGETS' bounding box; a query evaluates, with the brute force's own fma chain, only the references in
+ * sorted into a 64 x 8 x 8 grid (the wide search: 16^3) over the TARGETS' bounding box; a query evaluates, with the brute force's own fma chain, only the references in
  * the cells that the ball around it touches -- radius = its exact distance to a seed reference, widened by an explicit rounding margin
  * (csrc/ndp_nn_cells.inc) -- and keeps the smallest distance with the lowest index.  Bit-identical to ndp_chamfer_nn_fwd for ANY seeds.
  *   prev_idx_x [S] / prev_idx_y [T] (either may be NULL): seed indices, e.g. the previous call's idx_x / idx_y; an entry that is
@@ -605,7 +605,7 @@ typedef struct ndp_engine {
                                         keeps its value and meaning.  ndp_engine_load then also builds the grid of a slot's targets. */
     float *nnc_geom;                 /* [B][8] grid geometry per pair: origin[3], cells per unit length[3], 2 pad (NULL without nn_cells) */
     int *nnc_start;                  /* [B][NDP_NNC_START] cell_start of the targets' grid, x fastest (NULL without nn_cells)            */
-    float *nnc_rec;                  /* [B][t_cap][4] the targets sorted by cell: {x, y, z, index bits}, 16-byte aligned (NULL without)   */
+    float *nnc_rec;                  /* [B][t_cap][4] the targets sorted by cell: {index bits, x, y, z}, 16-byte aligned (NULL without) */
     int nn_cells_wide, pad_w;        /* ABI 208.  nn_cells_wide != 0: the nearest-neighbour stage is the grid ball search for up to 8192
                                         points per cloud (csrc/ndp_nn_cells_wide.inc: k_eng_nnw_sort + k_eng_nn_cells_wide, bit-identical
                                         results, needs ndp_engine_nn_cells_wide_fits(n_cap, t_cap)) in place of the dense kernel nn_mode
@@ -614,7 +614,7 @@ typedef struct ndp_engine {
                                         the warped sources' (rewritten every tick); nnc_rec [B][t_cap + n_cap][4]: the targets' records,
                                         then the warped sources'.  ndp_engine_load builds the grid of a slot's targets.                    */
 } ndp_engine;
-#define NDP_NNC_START 4104           /* ints per cell_start table: 16^3 + 1 entries, padded to a multiple of 4 */
+#define NDP_NNC_START 4104           /* ints per cell_start table: 4096 + 1 entries, padded to a multiple of 4 */
 
 /* Floats PER PAIR of the row-partial buffer of the one-pass nearest-neighbour kernel ({d2, idx} per source and
  * 128-target chunk).                                                                                             */

@@ -9,7 +9,13 @@ The committed output is profiles/nn_ball_sizing.txt.
 counts with the cell search's REAL geometry instead of a fixed cell size -- a G^3 grid over the targets' bounding box and the kernel's own
 float32 cell expression (nnc_cell1 of csrc/ndp_nn_cells.inc), warped sources clamped into border cells -- at every evaluation of levels 0, 4
 and 8 of the oracle's own optimisation loop (level forward / backward, Chamfer, Adam of oracle/ndp_oracle.py, bench.py's clouds and sampling).
-The committed output is profiles/nn_ball_sizing_wide.txt."""
+The committed output is profiles/nn_ball_sizing_wide.txt.
+    python tools/nn_ball_sizing.py steps [x | y | z] [GXxGYxGZ ...] [by_cell]
+replays config A's trajectories (the oracle's loop, NDP.yaml's 2000 samples, every evaluation and both directions) through the wave-step
+model of tools/nn_wave_steps.py: the kernel's lane mapping (query t + 1024 u, 64 lanes per wave), per wave and tick the modelled steps
+(sum over row iterations of the busiest lane's records, plus the longest lane's rows) and the ideal (rows + records over lanes), for grids of
+Gx x Gy x Gz <= 4096 cells whose row axis runs along the given geometric axis; by_cell deals the queries to the lanes in the order of their
+own cells.  The committed output is profiles/nn_wave_steps.txt."""
 import sys, os, torch, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -105,6 +111,73 @@ def wide(kind, grids, levels=(0, 4, 8), n_pairs=2, nthreads=16):
             print(f" G {G:2d} levels {levels} together: rows mean {a[:,0].mean():.5f} | cols mean {a[:,3].mean():.5f} | both directions {(a[:,0].mean() + a[:,3].mean()) / 2:.5f} of S*T")
 
 
+def steps(fine, shapes, n_pairs=2, nthreads=8, by_cell=False):
+    """The wave-step model of tools/nn_wave_steps.py over config A's own trajectories (the oracle's loop, every evaluation that has a previous
+    one, both directions).  fine: the geometric axis (0, 1, 2) that the grid's row axis runs along; shapes: (Gx, Gy, Gz) with Gx on that axis."""
+    import ctypes
+    import nn_wave_steps as W
+    from oracle import ndp_oracle as O
+    from deformationpyramid_amd.synthetic import synthetic_pair
+    from deformationpyramid_amd.config import load_config
+    from deformationpyramid_amd.nets import Deformation_Pyramid
+    cfg = load_config(os.path.join(ROOT, "config", "NDP.yaml"), device=0)
+    perm = [fine] + [a for a in range(3) if a != fine]         # the fine axis becomes the model's x
+    acc = {s: [] for s in shapes}                              # per tick and direction: (sum of steps, sum of row parts, sum of ideals, max steps, waves, rows, records, queries)
+    for k in range(n_pairs):
+        src, tgt, _, _ = synthetic_pair(k)
+        torch.manual_seed(k)
+        pyr = Deformation_Pyramid(depth=cfg.depth, width=cfg.width, device="cpu", k0=cfg.k0, m=cfg.m, rotation_format=cfg.rotation_format, motion=cfg.motion_type)
+        sc = src - src.mean(0, keepdim=True); tc = tgt - tgt.mean(0, keepdim=True)
+        x = sc[torch.randperm(sc.shape[0])[:cfg.samples]].contiguous().numpy()
+        y = tc[torch.randperm(tc.shape[0])[:cfg.samples]].contiguous().numpy()
+        yp = np.ascontiguousarray(y[:, perm])
+        geo = {s: W.geometry(yp, s) for s in shapes}
+        prev, ticks = None, 0
+        for level in range(cfg.m):
+            d = pyr.descs[level]
+            cd = O.make_desc(d.width, d.n_hidden, d.motion, d.rotfmt, d.nonrigidity, d.mlp_scale)
+            p = pyr.store[level, :d.param_count].numpy().copy()
+            am, av = np.zeros_like(p), np.zeros_like(p)
+            bc, lp = ctypes.c_int(0), ctypes.c_double(1e6)
+            warped = x
+            for it in range(cfg.iters):
+                warped = O.level_fwd(cd, p, level, cfg.k0, x, nthreads=nthreads)
+                r = O.chamfer(warped, y, want_grad=True, nthreads=nthreads)
+                ticks += 1
+                if prev is not None:
+                    wp = np.ascontiguousarray(warped[:, perm])
+                    for s in shapes:
+                        o, ih = geo[s]
+                        for q, ref, seed in ((wp, yp, prev[0]), (yp, wp, prev[1])):
+                            st, rows, ideal, nr, nc = W.direction(q, ref, seed, o, ih, s, by_cell)
+                            acc[s].append((st.sum(), rows.sum(), ideal.sum(), st.max(), len(st), nr, nc, q.shape[0]))
+                prev = (r["idx_x"].astype(np.int64), r["idx_y"].astype(np.int64))
+                if O.lib().ndp_o_stop_check(ctypes.c_double(float(r["loss"])), ctypes.byref(bc), ctypes.byref(lp), int(cfg.max_break_count),
+                                            ctypes.c_double(cfg.break_threshold_ratio)):
+                    break
+                g = O.level_bwd(cd, p, level, cfg.k0, x, r["gx"], nthreads=nthreads)
+                O.adam(p, g, am, av, it + 1, lr=cfg.lr)
+            x = warped
+        print(f"A pair {k}: S {x.shape[0]} T {y.shape[0]}, {ticks} evaluations, last loss {float(r['loss']):.5f}")
+    print(f"fine axis {'xyz'[fine]}{', queries dealt to the lanes in the order of their cells' if by_cell else ''}; per wave (64 lanes, one of a thread's two queries) and tick, mean over both directions of {n_pairs} pairs:")
+    print("   Gx  Gy  Gz | steps = rows + records | ideal | worst wave || per query: rows  records")
+    for s in shapes:
+        a = np.array(acc[s], np.float64)
+        w = a[:, 4].sum()
+        print(f"  {s[0]:3d} {s[1]:3d} {s[2]:3d} | {a[:,0].sum() / w:6.1f} = {a[:,1].sum() / w:5.1f} + {(a[:,0].sum() - a[:,1].sum()) / w:5.1f} | {a[:,2].sum() / w:5.1f} | "
+              f"{a[:,3].mean():6.1f}     ||   {a[:,5].sum() / a[:,7].sum():6.2f} {a[:,6].sum() / a[:,7].sum():7.2f}")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "steps":
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    by_cell = "by_cell" in sys.argv
+    args = [a for a in sys.argv[2:] if a != "by_cell"]
+    fine = "xyz".index(args[0]) if args else 0
+    grids = [tuple(int(v) for v in a.split("x")) for a in args[1:]] or \
+            [(16, 16, 16), (32, 16, 8), (32, 8, 16), (64, 8, 8), (64, 16, 4), (64, 4, 16), (128, 8, 4), (128, 4, 8), (256, 4, 4), (8, 16, 16), (16, 32, 8)]
+    assert all(len(g) == 3 and g[0] * g[1] * g[2] <= 4096 for g in grids), "Gx x Gy x Gz <= 4096 (the cell_start table stays 16 KB)"
+    steps(fine, grids, by_cell=by_cell)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] in ("C", "D"):
     wide(sys.argv[1], [int(v) for v in sys.argv[2:]] or [16])
     sys.exit(0)

@@ -93,6 +93,12 @@ class LoadJob(ctypes.Structure):
                 ("n_src", ctypes.c_int), ("n_tgt", ctypes.c_int)]
 
 
+class StageLaunch(ctypes.Structure):
+    """ndp_stage_launch: one launch of a tick as ndp_engine_plan reports it (extra: the kernel's third integer argument, or -1)."""
+    _fields_ = [("kernel", ctypes.c_char_p), ("stage", ctypes.c_int), ("grid", ctypes.c_int * 3), ("block", ctypes.c_int),
+                ("lds_bytes", ctypes.c_int), ("extra", ctypes.c_int)]
+
+
 MAX_WARP_JOBS = 32
 TICK_KERNELS = ("k_eng_fwd", "k_eng_nn", "k_eng_loss", "k_eng_bwd2", "k_eng_bwd1", "k_eng_update")   # one tick, launch order
 MAX_LOAD_JOBS = 16
@@ -233,6 +239,7 @@ _SIGS = {
     "ndp_engine_run_timed": [ctypes.POINTER(Engine), I, I, V, c_float_p],
     "ndp_engine_run_stages": [ctypes.POINTER(Engine), I, I, I, V],
     "ndp_engine_load": [ctypes.POINTER(Engine), I, ctypes.POINTER(LoadJob), I, V],
+    "ndp_engine_plan": [ctypes.POINTER(Engine), ctypes.POINTER(StageLaunch), c_int_p],
     "ndp_sinkhorn_schedule": [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double), I],
     "ndp_sinkhorn_workspace": [I, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_sinkhorn_divergence": [V, I, V, I, F, F, F, ctypes.c_double, V, V, V, V, V],
@@ -260,7 +267,8 @@ _SIGS = {
     "ndp_attention_backward": [V, V, V, V, V, V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, ctypes.c_double, V, V, V, V, V],
 }
 ABI_VERSION = 215                                   # the ABI this signature table was last renumbered at; entries added since (216:
-                                                    # ndp_attention_compat_forward; 217: ndp_attention_forward_lse, ndp_attention_backward)
+                                                    # ndp_attention_compat_forward; 217: ndp_attention_forward_lse, ndp_attention_backward;
+                                                    # 218: ndp_engine_plan)
                                                     # only append, and ndp_version() tells what a library has
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

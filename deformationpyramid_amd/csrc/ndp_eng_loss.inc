@@ -1,7 +1,9 @@
 // ndp_eng_loss.inc -- the engine's loss stage: loss, early-stop decision and dL/dx' of every pair (k_eng_loss).  Behind
 // ndp_nn_matrix.inc: the fold of the row partials asks which nearest-neighbour kernel wrote them.
 // Does the engine's nearest-neighbour stage run as k_eng_nn_mx8 (one workgroup and ONE row partial per 512 targets)?  The launcher and
-// the loss stage's fold of the row partials ask the same question.
+// the loss stage's fold of the row partials ask the same question.  The last clause holds for every n_cap (the static_assert beside
+// nn2_lds_floats): there is no other kernel of nn_mode 2.  It stays written out because the compiler does not fold it, and k_eng_loss
+// without it is other machine code.
 __host__ __device__ inline bool eng_nn_mx8(const ndp_engine &e) {
     return e.w_cd != 0.f && e.t_cap > 0 && e.nn_mode == 2 && nn2_lds_floats(e.n_cap, 8) * 4 <= 160 * 1024;
 }

@@ -20,7 +20,7 @@
 #include "ndp_eng_fwd.inc"             // engine forward stage on fp32 (k_eng_fwd); level_freq, xcd_pair_block, NDP_LROW for the stages below
 #include "ndp_fwd_split.inc"           // level forward on two-way fp16 splits: k_eng_fwd8, k_pyramid_fwd8; the plane-image format
 #include "ndp_nn_onepass.inc"          // one-pass NN on the vector pipe: k_eng_nn, k_eng_nn_lat8 / 16, k_nn1, k_nn1_rows
-#include "ndp_nn_matrix.inc"           // one-pass NN with the distances on the bf16 matrix pipe: k_eng_nn_mx / mx8, k_nn2
+#include "ndp_nn_matrix.inc"           // one-pass NN with the distances on the bf16 matrix pipe: k_eng_nn_mx8, k_nn2
 #include "ndp_eng_loss.inc"            // engine loss stage: loss, early-stop decision, dL/dx' (k_eng_loss)
 #include "ndp_eng_bwd.inc"             // engine backward stage on fp32: eng_bwd_job, k_eng_bwd2, k_eng_bwd1
 #include "ndp_bwd_split.inc"           // the two-launch backward on fp16 splits: k_eng_bwd2_8, k_eng_bwd1_8
@@ -32,7 +32,7 @@
 #include "ndp_eng_load.inc"            // pair preparation and slot (re)fill: k_pair_means*, LoadJobs, k_eng_load
 #include "ndp_nn_cells.inc"            // exact grid ball search (behind LoadJobs: its grid-build kernel rides behind k_eng_load)
 #include "ndp_nn_cells_wide.inc"       // the same search for clouds of up to 8192 points: grids sorted in global memory, queries split over workgroups
-#include "ndp_abi.inc"                 // host entries that choose between the files above: level / pyramid / engine load, tick, NN shapes, operators
+#include "ndp_abi.inc"                 // host entries that choose between the files above: level / pyramid / engine load, the tick's launch plan (plan_tick) and its launcher, NN shapes, operators
 #include "ndp_flow_metrics.inc"        // scene-flow metrics: k_flow_metrics, ndp_flow_metrics
 #include "ndp_nerfies.inc"             // Nerfies baseline
 #include "ndp_ed.inc"                  // embedded-deformation N-ICP baseline

@@ -27,12 +27,14 @@
 // NW waves per workgroup (4: 256 targets per chunk, two workgroups per CU; 8: 512 targets per chunk, one workgroup per CU -- the same
 // eight waves per CU, but the per-workgroup set-up (sources -> LDS, norms), the A operands of a source block and the row stage
 // (transposition + exact evaluation per source block and CHUNK) are paid once per 512 targets instead of once per 256)
-__host__ __device__ inline int nn2_nb(int n_cap) { return nn1_col_blocks(n_cap) < NN2_NB_MAX ? nn1_col_blocks(n_cap) : NN2_NB_MAX; }
-__host__ __device__ inline int nb_cap_floats(int nb, int nw) { return nb * 64 * nw + 3 * nb * NN1_XLD + nw * 32 * NN2_TS + 8; }
-__host__ __device__ inline int nn2_lds_floats(int n_cap, int nw = 4) {
+__host__ __device__ constexpr int nn2_nb(int n_cap) { return nn1_col_blocks(n_cap) < NN2_NB_MAX ? nn1_col_blocks(n_cap) : NN2_NB_MAX; }
+__host__ __device__ constexpr int nb_cap_floats(int nb, int nw) { return nb * 64 * nw + 3 * nb * NN1_XLD + nw * 32 * NN2_TS + 8; }
+__host__ __device__ constexpr int nn2_lds_floats(int n_cap, int nw = 4) {
     return ((4 * 64 * nw + nb_cap_floats(nn2_nb(n_cap), nw) + 3) & ~3) + 2 * nw * 2 * 64 * 4;
 }
-__host__ __device__ inline bool nn2_fits(int n_cap) { return nn2_lds_floats(n_cap) * 4 <= 80 * 1024; }
+// nn2_nb caps the resident blocks, so both carves have a worst case whatever n_cap is: no engine and no S is refused for its size
+static_assert(nn2_lds_floats(NN2_NB_MAX * NN1_XW, 4) * 4 <= 80 * 1024, "4 waves (k_nn2): two workgroups per CU");
+static_assert(nn2_lds_floats(NN2_NB_MAX * NN1_XW, 8) * 4 <= 160 * 1024, "8 waves (k_eng_nn_mx8): one workgroup per CU");
 
 // x = hi + mid + lo in bf16; a non-finite x (padding: +inf) stays in hi alone
 __device__ __forceinline__ void nn2_split3(float x, __bf16 &hi, __bf16 &mid, __bf16 &lo) {
@@ -475,12 +477,7 @@ __device__ __forceinline__ void eng_nn_mx_body(const ndp_engine &e, int parity, 
     const float *y = e.tgt + (size_t)b * e.t_cap * 3;
     nn2_body<NW>(xw, gm.S, y, gm.T, y0, e.t_cap, rowpart, e.d2y + (size_t)b * e.t_cap, iy, sm);
 }
-extern "C" __global__ void __launch_bounds__(256, 2)
-k_eng_nn_mx(ndp_engine e, int parity) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    eng_nn_mx_body<4>(e, parity, sm);
-}
-// 512 targets per workgroup, one 8-wave workgroup per CU (round 4; the engine's choice whenever its LDS carve fits)
+// 512 targets per workgroup, one 8-wave workgroup per CU (round 4): the engine's kernel of nn_mode 2
 extern "C" __global__ void __launch_bounds__(512, 1)
 k_eng_nn_mx8(ndp_engine e, int parity) {
     extern __shared__ __attribute__((aligned(16))) float sm[];

@@ -73,7 +73,7 @@ __device__ __forceinline__ float wave_colmin16(const float (&c)[16], int lane) {
 struct NnPart { float d2; int idx; };
 
 __host__ __device__ inline int nn1_row_chunks(int t_cap) { return (t_cap + NN1_YCH - 1) / NN1_YCH; }
-__host__ __device__ inline int nn1_col_blocks(int n_cap) { return (n_cap + NN1_XW - 1) / NN1_XW; }
+__host__ __device__ constexpr int nn1_col_blocks(int n_cap) { return (n_cap + NN1_XW - 1) / NN1_XW; }
 // dynamic LDS of the one-pass kernel (floats): target chunk, column table, re-scan results, (optionally) the sources
 __host__ __device__ inline int nn1_lds_floats(int n_cap, bool stage_x) {
     const int nb = nn1_col_blocks(n_cap);

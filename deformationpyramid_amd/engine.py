@@ -123,6 +123,20 @@ def resolve_nn_cells_wide(n_cap, t_cap, nn_mode_given, nn_mode, nn_cells, nn_cel
     return bool(nn_cells_wide)
 
 
+def tick_plan(c_engine):
+    """The launches one tick of the engine record `c_engine` (N.Engine) makes, as the library itself plans them (ndp_engine_plan: what
+    ndp_engine_run validates and chooses, without a HIP call -- it answers without a GPU): one list per stage, in N.TICK_KERNELS order,
+    of (kernel name, (grid x, y, z), threads per workgroup, dynamic LDS bytes, third integer argument | None).  Raises NdpError with
+    ndp_engine_run's own message where that would refuse the engine."""
+    rec = (N.StageLaunch * (2 * len(N.TICK_KERNELS)))()
+    n = ctypes.c_int()
+    N.check(N.lib().ndp_engine_plan(ctypes.byref(c_engine), rec, ctypes.byref(n)), "ndp_engine_plan")
+    stages = [[] for _ in N.TICK_KERNELS]
+    for r in rec[:n.value]:
+        stages[r.stage].append((r.kernel.decode(), tuple(r.grid), r.block, r.lds_bytes, None if r.extra < 0 else r.extra))
+    return stages
+
+
 class Snapshot:
     """Host copy of the [B] pair states of one tick."""
     __slots__ = ("raw", "sz", "level")
@@ -290,6 +304,10 @@ class BatchedEngine:
         N.check(self.lib.ndp_engine_run(ctypes.byref(self.c_engine), self.tick, int(n_ticks),
                                         N.stream_ptr(self.device)), "ndp_engine_run")
         self.tick += n_ticks
+
+    def plan(self):
+        """What one tick of this engine launches, per stage (tick_plan)."""
+        return tick_plan(self.c_engine)
 
     def run_stages(self, lo, hi):
         """Stages lo..hi (0 forward, 1 NN, 2 loss, 3 bwd2, 4 bwd1, 5 update) of the CURRENT tick; the tick counter advances

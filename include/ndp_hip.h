@@ -204,7 +204,9 @@ int ndp_chamfer_nn_onepass(const float *x, int S, const float *y, int T, float *
  * only SELECTS candidates -- every candidate within the rounding bound is re-evaluated with the exact fma chain, so d2 and the lowest
  * index are bit-identical to ndp_chamfer_nn_fwd.  2048 sources are resident in LDS at a time; more are walked in passes (highest
  * indices first, so the exact comparisons still end on the lowest index): no size limit since round 3
- * (ndp_engine_nn_matrix_fits(n_cap) is kept and returns 1).  ws_row as for ndp_chamfer_nn_onepass.                           */
+ * (ndp_engine_nn_matrix_fits(n_cap) is kept and returns 1: it cannot return anything else while the sources are walked in passes --
+ * at most 2048 of them are resident, so the LDS carve has a worst case that is checked when the library is compiled).
+ * ws_row as for ndp_chamfer_nn_onepass.                                                                                        */
 int ndp_chamfer_nn_matrix(const float *x, int S, const float *y, int T, float *d2x, int *idx_x, float *d2y,
                           int *idx_y, float *ws_row, void *stream);
 int ndp_engine_nn_matrix_fits(int n_cap);
@@ -593,7 +595,7 @@ typedef struct ndp_engine {
                                         No other bit is accepted (ABI 204: bits 64, 128, 256 and 512 selected measured variants,
                                         DESIGN.md section 0, and are refused).
                                         nn_mode 0: one-pass kernel, distances on the vector pipe; 2: the same on the bf16 matrix pipe
-                                        with exact re-evaluation (bit-identical, needs ndp_engine_nn_matrix_fits(n_cap)); 1: latency
+                                        with exact re-evaluation (bit-identical, any n_cap: k_eng_nn_mx8); 1: latency
                                         shape -- two passes in 64-query workgroups, S/64 + T/64 of them per pair -- for a handful of
                                         resident pairs   */
     unsigned int *gmax;              /* [B] bit pattern of max |dO| of the pair this tick (zeroed by the forward stage, raised by
@@ -657,6 +659,20 @@ int ndp_engine_run_timed(const ndp_engine *e, int tick0, int n_ticks, void *stre
  * dL/dx', 3 bwd2, 4 bwd1, 5 update.  Test and measurement aid: the buffers a kernel leaves behind (act, heads, dO, gpart) can be
  * read between stages; the stages 0..5 of a tick run in order, in any grouping, equal ndp_engine_run(e, tick, 1).               */
 int ndp_engine_run_stages(const ndp_engine *e, int tick, int stage_lo, int stage_hi, void *stream);
+
+/* ABI 218.  The launches ONE tick of `e` makes, in launch order, without making them: what ndp_engine_run validates and chooses
+ * (the same checks, codes and messages), and nothing else -- no HIP call, no buffer of the engine is dereferenced, so it answers on
+ * a machine without a GPU.  A stage has zero launches (stage 4 under the fused or generic backward, stage 1 without a Chamfer
+ * term), one, or two (stage 1 of nn_cells_wide: sort, then search).  out [2 * NDP_TICK_KERNELS], *n_out = records written.     */
+typedef struct ndp_stage_launch {
+    const char *kernel;              /* the kernel's name, a string literal of the library                                    */
+    int stage;                       /* 0..NDP_TICK_KERNELS - 1                                                               */
+    int grid[3], block;              /* workgroups x, y, z; threads per workgroup                                             */
+    int lds_bytes;                   /* dynamic LDS of the launch                                                             */
+    int extra;                       /* the kernel's third integer argument (k_eng_nn: stage_x; k_eng_fwd8: warp_tail, 1 = the points
+                                        are warped behind the tile loop; k_eng_nn_cells_wide: query chunks Q), -1 where it takes none     */
+} ndp_stage_launch;
+int ndp_engine_plan(const ndp_engine *e, ndp_stage_launch *out, int *n_out);
 
 #ifdef __cplusplus
 }

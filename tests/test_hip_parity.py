@@ -851,6 +851,35 @@ def test_engine_nn_shapes_are_bit_identical(dev):
         assert torch.equal(runs[0][0], other[0]) and torch.equal(runs[0][2], other[2]) and torch.equal(runs[0][3], other[3])
 
 
+def test_engines_of_growing_capacity_share_a_process(dev):
+    """k_eng_nn and k_nn1 ask for an LDS table that grows with the source capacity, and the launcher remembers per kernel what it has
+    asked the runtime for: a small engine first (n_cap = 64), then one whose column table plus staged sources is 16 843 floats =
+    67 372 bytes (n_cap = 3200: the first size above 64 KB) -- the second one's nearest neighbours are the brute force's, bit for
+    bit.  The same small-then-large pair for the operator form of the kernel."""
+    from deformationpyramid_amd import ops
+    from deformationpyramid_amd.engine import BatchedEngine, OptConfig
+    cfg = OptConfig(m=1, iters=2, early_stop=False, w_cd=1.0, trunc=1e9)
+    pyr = seeded_pyramid(3, m=1, **VARIANTS["se3aa"])
+    for n_cap, t_cap in ((64, 64), (3200, 256)):
+        eng = BatchedEngine(pyr.descs[0], cfg, 1, n_cap=n_cap, t_cap=t_cap, device=dev, G=1, nn_mode=0, gemm_mode=0)
+        S, T = n_cap - 3, t_cap - 5
+        assert (eng.n_cap, eng.t_cap, eng.nn_cells, eng.nn_cells_wide) == (n_cap, t_cap, False, False)
+        assert eng.plan()[1] == [("k_eng_nn", (1, 1, 1), 256, 4 * (768 + -(-n_cap // 128) * (256 + 3 * 129)), 1)]
+        eng.load(0, cloud(S, 11), 0, S, None, cloud(T, 12) + 0.02, pyr.store)
+        if n_cap == 64:
+            eng.run_ticks(1)
+            torch.cuda.synchronize()
+            continue
+        eng.run_stages(0, 1)
+        d2x, ix, d2y, iy = ops.chamfer_nn(eng.pts[0, 1, :S].contiguous(), eng.tgt[0, :T].contiguous())
+        assert torch.equal(eng.idx_y[0, :T], iy) and torch.equal(eng.d2y[0, :T], d2y)
+        assert int(iy.min()) >= 0 and len(set(iy.tolist())) > T // 4     # (a search worth the name: the targets do not share a neighbour)
+    for S in (64, 3200):
+        x, y = cloud(S, 13).to(dev), (cloud(250, 14) + 0.02).to(dev)
+        for got, want in zip(ops.chamfer_nn_onepass(x, y), ops.chamfer_nn(x, y)):
+            assert torch.equal(got, want), S
+
+
 @pytest.mark.parametrize("gemm_mode", [1, 2, 3, 4, 5, 6, 7])
 @pytest.mark.parametrize("tag", ["se3aa", "sim3eu", "sflow"])
 def test_engine_on_fp16_splits_stays_inside_the_parity_budget(dev, tag, gemm_mode):

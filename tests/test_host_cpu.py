@@ -24,6 +24,7 @@ def test_abi_library_loads_and_exports_declared_symbols():
     assert declared == set(_native.EXPORTS), declared ^ set(_native.EXPORTS)
     for name in declared:
         assert getattr(L, name) is not None
+    assert "ndp_engine_plan" in declared
     L.ndp_version.restype = ctypes.c_int
     assert L.ndp_version() >= 100
 
@@ -36,6 +37,8 @@ def test_struct_layouts_match_the_header():
     assert _native.Engine.break_threshold_ratio.offset % 8 == 0
     assert _native.Engine.geom.offset % 8 == 0
     assert ctypes.sizeof(_native.WarpJob) == 48 and ctypes.sizeof(_native.LoadJob) == 88     # 5 / 8 pointers + 2 / 6 ints
+    launch = _native.StageLaunch                                 # ndp_stage_launch: the name, then seven ints
+    assert ctypes.sizeof(launch) == 40 and [getattr(launch, f).offset for f, _ in launch._fields_] == [0, 8, 12, 24, 28, 32]
     header = open(os.path.join(ROOT, "include", "ndp_hip.h")).read()
     assert int(re.search(r"#define NDP_MAX_WARP_JOBS (\d+)", header).group(1)) == _native.MAX_WARP_JOBS
     assert int(re.search(r"#define NDP_MAX_LOAD_JOBS (\d+)", header).group(1)) == _native.MAX_LOAD_JOBS

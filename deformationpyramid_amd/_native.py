@@ -259,6 +259,9 @@ _SIGS = {
     "ndp_radius_search": [V, V, c_int_p, c_int_p, I, F, I, V, ctypes.c_longlong, V, V, V, V],
     "ndp_kpconv_forward_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, ctypes.POINTER(ctypes.c_longlong)],
     "ndp_kpconv_forward": [V, V, V, V, V, V, ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, F, I, I, I, V, ctypes.c_longlong, V, V],
+    "ndp_kpconv_backward_workspace": [ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
+    "ndp_kpconv_backward": [V, V, V, V, V, V, V, ctypes.c_longlong, ctypes.c_longlong, I, I, I, I, F, I, I, I, ctypes.c_longlong, V,
+                            ctypes.c_longlong, V, V, V],
     "ndp_attention_forward": [V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, V, V],
     "ndp_attention_compat_forward": [V, V, V, V, V, V, V, V, V, c_int_p, c_int_p, I, I, I, F, ctypes.c_double, V, V],
     "ndp_feat_conf_workspace": [I, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
@@ -268,7 +271,8 @@ _SIGS = {
 }
 ABI_VERSION = 215                                   # the ABI this signature table was last renumbered at; entries added since (216:
                                                     # ndp_attention_compat_forward; 217: ndp_attention_forward_lse, ndp_attention_backward;
-                                                    # 218: ndp_engine_plan)
+                                                    # 218: ndp_engine_plan; 219: ndp_kpconv_backward_workspace, ndp_kpconv_backward,
+                                                    # next to the forward's as ndp_engine_plan is next to the engine's)
                                                     # only append, and ndp_version() tells what a library has
 EXPORTS = ["ndp_version", "ndp_last_error", "ndp_build_id", "ndp_abi_sizes", "ndp_engine_nn_workspace"] + list(_SIGS)
 

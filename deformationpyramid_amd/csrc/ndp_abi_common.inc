@@ -65,10 +65,10 @@ static int check_offsets(const char *who, const int *off_host, int B, int min_ro
 
 // Raise a kernel's dynamic-LDS attribute to `bytes`, once per thread and size: the table keeps the largest size asked per kernel, and
 // a kernel whose size grows with the problem (k_eng_nn, k_nn1, ...) goes to the runtime again when a caller asks for more.  One slot
-// per kernel that is ever passed here: 39 named ones (10 level / pyramid, 4 Jacobian / inverse, 2 baseline, k_kpc_forward, the 16 a
-// tick plan can name and k_eng_nn_cells_build, 5 NN operators) and the 6 attention families x {scalar, v4} x 4 head widths.  A full
-// table only costs the runtime call every time.
-static constexpr int kSmemKernels = 39 + 6 * 2 * 4;
+// per kernel that is ever passed here: 41 named ones (10 level / pyramid, 4 Jacobian / inverse, 2 baseline, k_kpc_forward, k_kpb_edge,
+// k_kpb_dw, the 16 a tick plan can name and k_eng_nn_cells_build, 5 NN operators) and the 6 attention families x {scalar, v4} x 4 head
+// widths.  A full table only costs the runtime call every time.
+static constexpr int kSmemKernels = 41 + 6 * 2 * 4;
 static int set_smem(const void *fn, int bytes) {
     static thread_local struct { const void *fn; int bytes; } set[kSmemKernels];
     auto *slot = set;
@@ -112,7 +112,8 @@ extern "C" int ndp_debug_phase_read(unsigned long long *out64, int reset) {
 //   216: ndp_attention_compat_forward
 //   217: ndp_attention_forward_lse, ndp_attention_backward
 //   218: ndp_engine_plan (ndp_stage_launch); k_eng_nn_mx is gone, ndp_engine_nn_matrix_fits answers 1 for every n_cap
-extern "C" int ndp_version(void) { return 218; }
+//   219: ndp_kpconv_backward_workspace, ndp_kpconv_backward
+extern "C" int ndp_version(void) { return 219; }
 extern "C" const char *ndp_last_error(void) { return g_err; }
 static const char k_build_tag[] = "NDP_BUILD_ID=" NDP_BUILD_ID;        // the loader finds this tag in the file without loading it
 extern "C" const char *ndp_build_id(void) { return k_build_tag + 13; }

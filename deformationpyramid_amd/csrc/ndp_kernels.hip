@@ -43,4 +43,5 @@
 #include "ndp_match.inc"               // descriptor matching: S x T row statistics on the f32 MFMA, dual-softmax / dustbin OT / mutual-NN
 #include "ndp_kpconv.inc"              // KPConv inputs: voxel barycentre subsampling and fixed-radius neighbours on a sorted cell-key table
 #include "ndp_kpconv_conv.inc"         // KPConv convolution: neighbour aggregation and the contraction with the kernel weights on the f32 MFMA, one launch
-#include "ndp_attention.inc"           // multi-head soft-max attention with rotary codes, fused: scores and P V on the f32 MFMA, online soft-max
+#include "ndp_kpconv_bwd.inc"          // KPConv backward in the features and the weights: transposed neighbour table, slabbed edge gradients, blocked dW
+#include "ndp_attention.inc"          // multi-head soft-max attention with rotary codes, fused: scores and P V on the f32 MFMA, online soft-max

@@ -3,7 +3,11 @@ between kpconv.build_pyramid (the collate's tables) and matching.* (per-point de
 parameter and buffer names, so the `backbone.*` part of a Lepard checkpoint loads with load_state_dict(strict=True).
 
 What runs where: every KPConv is one ops.kpconv call (csrc/ndp_kpconv_conv.inc); the unary layers, the instance norm, LeakyReLU(0.1)
-and the two shadow-row gathers (max_pool, closest_pool) are torch ops on the device.  Forward only: ops.kpconv has no backward.
+and the two shadow-row gathers (max_pool, closest_pool) are torch ops on the device.  `forward` is the inference path: its KPConv
+outputs carry no grad_fn.  `forward_grad` (KPConv, SimpleBlock, ResnetBottleneckBlock, KPFCN) is the same computation on
+ops.kpconv_fn, whose backward is csrc/ndp_kpconv_bwd.inc: gradients reach every KPConv's weights and the input features, the torch
+ops around it are autograd's.  train_step is one optimiser step on a descriptor loss over synthetic surface pairs.  The points and
+the kernel points get no gradient.
 
 Not served: deformable / modulated convolutions, the `equivariant` / `invariant` block names, any `phase` but "coarse" (the
 reference's fine decoder is commented out upstream; `fine_out` is kept as unused parameters so that checkpoints load).  Lepard's
@@ -13,6 +17,7 @@ Lepard checkpoint is unverified: none is available."""
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn.init import kaiming_uniform_
@@ -87,6 +92,11 @@ class KPConv(nn.Module):
         return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points, self.KP_extent,
                           influence=self.KP_influence, aggregation=self.aggregation_mode, normalize=True)
 
+    def forward_grad(self, q_pts, s_pts, neighb_inds, x):
+        """forward's bits, differentiable in x and self.weights (ops.kpconv_fn)."""
+        return ops.kpconv_fn(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points, self.KP_extent,
+                             influence=self.KP_influence, aggregation=self.aggregation_mode, normalize=True)
+
     def __repr__(self):
         return f"KPConv(radius: {self.radius:.2f}, extent: {self.KP_extent:.2f}, in_feat: {self.in_channels:d}, out_feat: {self.out_channels:d})"
 
@@ -147,8 +157,14 @@ class SimpleBlock(nn.Module):
         self.leaky_relu = nn.LeakyReLU(0.1)
 
     def forward(self, x, batch):
+        return self._run(x, batch, self.KPConv)
+
+    def forward_grad(self, x, batch):
+        return self._run(x, batch, self.KPConv.forward_grad)
+
+    def _run(self, x, batch, conv):
         q_pts, s_pts, inds = _conv_tables(self.block_name, self.layer_ind, batch)
-        return self.leaky_relu(self.batch_norm(self.KPConv(q_pts, s_pts, inds, x)))
+        return self.leaky_relu(self.batch_norm(conv(q_pts, s_pts, inds, x)))
 
 
 class ResnetBottleneckBlock(nn.Module):
@@ -167,9 +183,15 @@ class ResnetBottleneckBlock(nn.Module):
         self.leaky_relu = nn.LeakyReLU(0.1)
 
     def forward(self, features, batch):
+        return self._run(features, batch, self.KPConv)
+
+    def forward_grad(self, features, batch):
+        return self._run(features, batch, self.KPConv.forward_grad)
+
+    def _run(self, features, batch, conv):
         q_pts, s_pts, inds = _conv_tables(self.block_name, self.layer_ind, batch)
         x = self.unary1(features)
-        x = self.leaky_relu(self.batch_norm_conv(self.KPConv(q_pts, s_pts, inds, x)))
+        x = self.leaky_relu(self.batch_norm_conv(conv(q_pts, s_pts, inds, x)))
         x = self.unary2(x)
         shortcut = max_pool(features, inds) if "strided" in self.block_name else features
         return self.leaky_relu(x + self.unary_shortcut(shortcut))
@@ -252,18 +274,27 @@ class KPFCN(nn.Module):
         self.fine_out = nn.Conv1d(out_dim, config.fine_feature_dim, kernel_size=1, bias=True)      # unused: the reference's fine phase is commented out
 
     def forward(self, batch, phase="coarse"):
+        return self._run(batch, phase, False)
+
+    def forward_grad(self, batch, phase="coarse"):
+        """forward's computation with every KPConv on ops.kpconv_fn: differentiable in the parameters and in batch["features"]
+        (which is used as it is, not detached)."""
+        return self._run(batch, phase, True)
+
+    def _run(self, batch, phase, grad):
         if phase != "coarse":
             raise NotImplementedError(f"phase {phase!r}: only the coarse descriptors are served")
-        x = batch["features"].clone().detach()
+        x = batch["features"] if grad else batch["features"].clone().detach()
+        call = (lambda op: getattr(op, "forward_grad", op)) if grad else (lambda op: op)
         skip_x = []
         for block_i, block_op in enumerate(self.encoder_blocks):
             if block_i in self.encoder_skips:
                 skip_x.append(x)
-            x = block_op(x, batch)
+            x = call(block_op)(x, batch)
         for block_i, block_op in enumerate(self.decoder_blocks):
             if block_i in self.decoder_concats:
                 x = torch.cat([x, skip_x.pop()], dim=1)
-            x = block_op(x, batch)
+            x = call(block_op)(x, batch)
             if block_i == 1:
                 return self.coarse_out(x.t().unsqueeze(0)).squeeze(0).t().contiguous()       # [N, C] -> [1, C, N] -> [N, C2]
         raise ValueError("the architecture has no unary block behind its first upsampling: no coarse descriptors")
@@ -282,3 +313,82 @@ def coarse_features(model, points, lengths, config, neighborhood_limits):
     feats = model(batch, phase="coarse")
     level = len(batch["points"]) - 2                               # one upsampling above the encoder's last level
     return batch["points"][level], batch["stack_lengths"][level], feats
+
+
+# ------------------------------------------------------------------------------------------ training the coarse descriptors
+TRAIN_LIMITS = (24, 28, 32, 36, 40)          # neighbourhood limits of synthetic_batch's pyramid, one per level
+TRAIN_TEMPERATURE = 0.1
+
+
+def trainable_parameters(model):
+    """The parameters the coarse phase reaches, for an optimiser.  What it does not reach -- coarse_in, fine_out and the decoder
+    behind the first unary -- is frozen (requires_grad_(False)): it would get no gradient and an optimiser would carry it unmoved."""
+    for name, p in model.named_parameters():
+        unused = name.startswith(("coarse_in.", "fine_out.")) or (name.startswith("decoder_blocks.") and int(name.split(".")[1]) > 1)
+        if unused:
+            p.requires_grad_(False)
+    return [p for p in model.parameters() if p.requires_grad]
+
+
+def synthetic_batch(seed, config, n_points=2048, device="cuda", match_radius=None):
+    """A seeded training pair as KPFCN's batch dict.  Both clouds are samples of synthetic.surface_pair's star-shaped surface
+    (synthetic.surface_radius), drawn independently with numpy's MT19937 in float64 (the same numbers on every machine); the target
+    is the surface rotated by synthetic.SURFACE_ROT_Z about z and translated by synthetic.SURFACE_TRN -- a known rigid motion.  On top
+    of kpconv.build_pyramid's lists and features = ones [N, 1]: "coarse_lengths" (source, target) at the level of the descriptors,
+    and "matches" [2, M] int64 -- the ground-truth coarse matches: the mutual nearest neighbours of the moved source coarse points
+    among the target's within match_radius (default: the coarse voxel edge), as indices into either side."""
+    from . import synthetic
+    config = _cfg(config)
+    rs = np.random.RandomState(seed)
+    d = rs.standard_normal((2 * n_points, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    ph = rs.uniform(0.0, 2.0 * math.pi, 4)
+    x = d * synthetic.surface_radius(d, ph, np)[:, None]
+    c, s = math.cos(synthetic.SURFACE_ROT_Z), math.sin(synthetic.SURFACE_ROT_Z)
+    Rz, t = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]), np.array(synthetic.SURFACE_TRN)
+    src, tgt = x[:n_points], x[n_points:] @ Rz.T + t
+    points = torch.from_numpy(np.concatenate([src, tgt]).astype(np.float32)).to(device)
+    n_layers = len(kpconv._layers(config.architecture))
+    batch = kpconv.build_pyramid(points, [n_points, n_points], config.first_subsampling_dl, config.conv_radius, config.deform_radius,
+                                 config.architecture, TRAIN_LIMITS[:n_layers])
+    batch["features"] = torch.ones(points.shape[0], 1, device=points.device)
+    level = len(batch["points"]) - 2
+    n_s, n_t = (int(v) for v in batch["stack_lengths"][level])
+    coarse = batch["points"][level]
+    moved = coarse[:n_s] @ torch.from_numpy(Rz.T.astype(np.float32)).to(coarse.device) + torch.from_numpy(t.astype(np.float32)).to(coarse.device)
+    radius = match_radius if match_radius is not None else config.first_subsampling_dl * 2 ** level
+    batch["coarse_lengths"] = (n_s, n_t)
+    batch["matches"] = kpconv.mutual_nn_correspondence(moved.contiguous(), coarse[n_s:].contiguous(), radius)
+    return batch
+
+
+def descriptor_scores(feats, batch, temperature=TRAIN_TEMPERATURE):
+    """a [n_s, n_t] = <f_s, f_t> / (C temperature) of a batch's coarse descriptors: ops.feat_conf's scores, in eager torch."""
+    n_s, n_t = batch["coarse_lengths"]
+    return feats[:n_s] @ feats[n_s:n_s + n_t].t() / (feats.shape[1] * temperature)
+
+
+def descriptor_loss(feats, batch, temperature=TRAIN_TEMPERATURE):
+    """The mean negative log dual-softmax likelihood of the batch's ground-truth matches: -mean_m (log softmax_j a[i_m, :][j_m] + log
+    softmax_i a[:, j_m][i_m]).  Eager torch: ops.feat_conf has no backward."""
+    a = descriptor_scores(feats, batch, temperature)
+    i, j = batch["matches"]
+    return -(torch.log_softmax(a, 1)[i, j] + torch.log_softmax(a, 0)[i, j]).mean()
+
+
+@torch.no_grad()
+def match_recall(feats, batch):
+    """The share of the ground-truth matches that the descriptors' mutual nearest neighbours (by score) recover."""
+    a = descriptor_scores(feats, batch)
+    i, j = batch["matches"]
+    return float(((a.argmax(1)[i] == j) & (a.argmax(0)[j] == i)).float().mean())
+
+
+def train_step(model, batches, optimizer):
+    """One optimiser step on the mean descriptor_loss of `batches` (synthetic_batch's dicts) through forward_grad -> the loss before
+    the step.  Every KPConv gradient is csrc/ndp_kpconv_bwd.inc's; the loss and everything between the convolutions is eager torch."""
+    optimizer.zero_grad(set_to_none=True)
+    loss = torch.stack([descriptor_loss(model.forward_grad(b, phase="coarse"), b) for b in batches]).mean()
+    loss.backward()
+    optimizer.step()
+    return loss.detach()

@@ -721,15 +721,9 @@ KPCONV_AGGREGATION = {"sum": 0, "closest": 1}
 KPCONV_MAX_K, KPCONV_MAX_C = 32, 1024
 
 
-def kpconv(q, s, idx, x, weights, kernel_points, extent, influence="linear", aggregation="sum", normalize=True):
-    """Rigid KPConv forward (csrc/ndp_kpconv_conv.inc: k_kpc_forward, both products on the f32-input MFMA) -> y [Nq, Cout].
-    q [Nq,3] queries, s [Ns,3] supports, idx [Nq,H] int32 or int64 stacked support rows (radius_search's; every value outside
-    0 .. Ns-1 is a shadow and contributes nothing), x [Ns,Cin] features (made contiguous if they are not), weights [K,Cin,Cout],
-    kernel_points [K,3].  y[n] = sum_k sum_c (sum_h w(n,h,k) x[idx[n,h],c]) W[k,c,:] with the kernel-point influence w of the
-    squared distance between s[idx[n,h]] - q[n] and kernel_points[k]: "constant" 1, "linear" max(0, 1 - d / extent), "gaussian"
-    exp(-d^2 / (2 (0.3 extent)^2 + 1e-9)); aggregation "closest" keeps, per neighbour, only its nearest kernel point; normalize
-    divides by max(1, number of neighbours whose feature row sums to a positive number), the reference's term.  K <= 32, H <= 64,
-    Cin, Cout <= 1024.  Forward only; does not synchronise."""
+def _kpconv_args(q, s, idx, x, weights, kernel_points, extent, influence, aggregation, dy=None):
+    """ops.kpconv's argument checks, shared with ops.kpconv_bwd (which passes dy, checked against [Nq, Cout] before the tensors are
+    asked to be on the device) -> (idx int32 contiguous, x contiguous, extent, (nq, ns, H, K, cin, cout))."""
     _stacked(q, "q"); _stacked(s, "s")
     nq, ns, extent = q.shape[0], s.shape[0], float(extent)
     if not isinstance(idx, torch.Tensor) or idx.ndim != 2 or idx.shape[0] != nq or idx.shape[1] < 1 or idx.dtype not in (torch.int32, torch.int64):
@@ -752,18 +746,65 @@ def kpconv(q, s, idx, x, weights, kernel_points, extent, influence="linear", agg
     if H > RADIUS_MAX_K or K > KPCONV_MAX_K or cin > KPCONV_MAX_C or cout > KPCONV_MAX_C:
         raise ValueError(f"served are H <= {RADIUS_MAX_K}, K <= {KPCONV_MAX_K}, Cin, Cout <= {KPCONV_MAX_C}; got H = {H}, K = {K}, "
                          f"Cin = {cin}, Cout = {cout}")
+    if dy is not None and (not isinstance(dy, torch.Tensor) or tuple(dy.shape) != (nq, cout)):
+        raise ValueError(f"dy must be [Nq, Cout] = [{nq}, {cout}], got {getattr(dy, 'shape', type(dy))}")
     _chk(q, "q"); _chk(s, "s")
     if idx.dtype == torch.int64:                                   # the reference's tables; a value beyond int32 is a shadow either way
         idx = idx.clamp(-1, ns).to(torch.int32)
     idx, x = idx.contiguous(), x.contiguous()
     _chk(idx, "idx", torch.int32); _chk(x, "x"); _chk(weights.detach(), "weights"); _chk(kernel_points.detach(), "kernel_points")
+    return idx, x, extent, (nq, ns, H, K, cin, cout)
+
+
+def kpconv(q, s, idx, x, weights, kernel_points, extent, influence="linear", aggregation="sum", normalize=True):
+    """Rigid KPConv forward (csrc/ndp_kpconv_conv.inc: k_kpc_forward, both products on the f32-input MFMA) -> y [Nq, Cout].
+    q [Nq,3] queries, s [Ns,3] supports, idx [Nq,H] int32 or int64 stacked support rows (radius_search's; every value outside
+    0 .. Ns-1 is a shadow and contributes nothing), x [Ns,Cin] features (made contiguous if they are not), weights [K,Cin,Cout],
+    kernel_points [K,3].  y[n] = sum_k sum_c (sum_h w(n,h,k) x[idx[n,h],c]) W[k,c,:] with the kernel-point influence w of the
+    squared distance between s[idx[n,h]] - q[n] and kernel_points[k]: "constant" 1, "linear" max(0, 1 - d / extent), "gaussian"
+    exp(-d^2 / (2 (0.3 extent)^2 + 1e-9)); aggregation "closest" keeps, per neighbour, only its nearest kernel point; normalize
+    divides by max(1, number of neighbours whose feature row sums to a positive number), the reference's term.  K <= 32, H <= 64,
+    Cin, Cout <= 1024.  The result carries no grad_fn: kpconv_fn is the differentiable form and kpconv_bwd the gradient itself.
+    Does not synchronise."""
+    idx, x, extent, dims = _kpconv_args(q, s, idx, x, weights, kernel_points, extent, influence, aggregation)
+    nq, ns, H, K, cin, cout = dims
     dev = q.device
-    ws = _workspace("ndp_kpconv_forward_workspace", (nq, ns, H, K, cin, cout), dev, torch.int32, per=4)
+    ws = _workspace("ndp_kpconv_forward_workspace", dims, dev, torch.int32, per=4)
     y = torch.empty(nq, cout, device=dev)
     N.check(N.lib().ndp_kpconv_forward(_p(q), _p(s), _p(idx), _p(x), _p(weights), _p(kernel_points), nq, ns, H, K, cin, cout, extent,
                                        KPCONV_INFLUENCE[influence], KPCONV_AGGREGATION[aggregation], int(bool(normalize)), _p(ws),
                                        4 * ws.numel(), _p(y), N.stream_ptr(dev)), "ndp_kpconv_forward")
     return y
+
+
+def kpconv_bwd(q, s, idx, x, weights, kernel_points, extent, dy, influence="linear", aggregation="sum", normalize=True, need_dx=True,
+               need_dw=True, slab_queries=0):
+    """The gradient of sum(kpconv(...) * dy) in x and in weights -> (dx [Ns,Cin] or None, dW [K,Cin,Cout] or None), given dy [Nq,Cout]
+    (csrc/ndp_kpconv_bwd.inc: fp32 on the f32-input MFMA, no atomics, every sum in one fixed order, the same bits run to run; the
+    influences are recomputed from the points, nothing of the forward is kept).  The normalisation count and the `closest` choice are
+    constants; the points and kernel_points get no gradient.  dx[r] is one chain over the incoming edges of r in ascending (n, h);
+    the per-edge gradients pass through memory in slabs of slab_queries queries (0: as many as 64 MiB hold; else a multiple of 16),
+    and the bits of dx do not depend on that.  need_dx / need_dw = False skips that gradient and its launches.  Takes kpconv's
+    checks; dy is made contiguous if it is not.  Does not synchronise."""
+    if not (need_dx or need_dw):
+        raise ValueError("need_dx and need_dw are both False: nothing to compute")
+    slab_queries = int(slab_queries)
+    if slab_queries < 0 or slab_queries % 16:
+        raise ValueError(f"slab_queries must be 0 or a positive multiple of 16, got {slab_queries}")
+    if dy is None:
+        raise ValueError("dy must be [Nq, Cout], got None")
+    idx, x, extent, dims = _kpconv_args(q, s, idx, x, weights, kernel_points, extent, influence, aggregation, dy)
+    nq, ns, H, K, cin, cout = dims
+    dy = _chk(dy.contiguous() if dy.is_cuda else dy, "dy")
+    dev = q.device
+    ws = _workspace("ndp_kpconv_backward_workspace", dims + (slab_queries,), dev, torch.int32, per=4)
+    dx = torch.empty(ns, cin, device=dev) if need_dx else None
+    dw = torch.empty(K, cin, cout, device=dev) if need_dw else None
+    N.check(N.lib().ndp_kpconv_backward(_p(q), _p(s), _p(idx), _p(x), _p(weights.detach()), _p(kernel_points.detach()), _p(dy), nq, ns, H, K,
+                                        cin, cout, extent, KPCONV_INFLUENCE[influence], KPCONV_AGGREGATION[aggregation],
+                                        int(bool(normalize)), slab_queries, _p(ws), 4 * ws.numel(), _p(dx), _p(dw), N.stream_ptr(dev)),
+            "ndp_kpconv_backward")
+    return dx, dw
 
 
 def landmark_mse(x, t):
@@ -925,6 +966,32 @@ def attention_fn(q, k, v, n_head, pe_q=None, pe_k=None, scale=None, offsets_q=No
     """attention, differentiable (first derivatives) in q, k and v: the forward keeps (q, k, v, o, lse) and the backward is one
     attention_bwd call.  The codes, the positions and everything else are constants."""
     return _AttentionFn.apply(q, k, v, n_head, pe_q, pe_k, scale, offsets_q, offsets_k, pos_q, pos_k, sigma_spat)
+
+
+class _KPConvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, s, idx, x, weights, kernel_points, extent, influence, aggregation, normalize):
+        xd, wd = x.detach().contiguous(), weights.detach()
+        ctx.args = dict(influence=influence, aggregation=aggregation, normalize=normalize)
+        ctx.extent = extent
+        ctx.save_for_backward(q.detach(), s.detach(), idx, xd, wd, kernel_points.detach())
+        return kpconv(q.detach(), s.detach(), idx, xd, wd, kernel_points.detach(), extent, **ctx.args)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        q, s, idx, x, w, kp = ctx.saved_tensors
+        need_dx, need_dw = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        dx = dw = None
+        if need_dx or need_dw:
+            dx, dw = kpconv_bwd(q, s, idx, x, w, kp, ctx.extent, dy.contiguous(), need_dx=need_dx, need_dw=need_dw, **ctx.args)
+        return None, None, None, dx, dw, None, None, None, None, None
+
+
+def kpconv_fn(q, s, idx, x, weights, kernel_points, extent, influence="linear", aggregation="sum", normalize=True):
+    """kpconv, differentiable (first derivatives) in x and in weights: the forward is kpconv's, bit for bit, and keeps only its inputs;
+    the backward is one kpconv_bwd call for what needs_input_grad asks.  The points, the table and kernel_points are constants."""
+    return _KPConvFn.apply(q, s, idx, x, weights, kernel_points, float(extent), influence, aggregation, bool(normalize))
 
 
 def flow_metrics(flow, flow_gt, overlap=None):

@@ -425,7 +425,8 @@ int ndp_radius_search(const float *q, const float *s, const int *q_lengths_host,
  *                division; the flag of a support row is computed once per call in a fixed order.  normalize 0: the plain sum.
  * Both products run on the f32-input MFMA (exact fp32 products, one rounding per term, a fixed order); there are no atomics, the
  * same inputs give the same bits, and a query's result does not depend on the other queries of the call.  Nothing is
- * data-dependent: ndp_kpconv_forward launches on `stream` and DOES NOT synchronise.  No backward pass.
+ * data-dependent: ndp_kpconv_forward launches on `stream` and DOES NOT synchronise.  The backward pass in x and W:
+ * ndp_kpconv_backward below (ABI 219).
  * ws: at least ndp_kpconv_forward_workspace(...) bytes (the row flags), 16-byte aligned; ws_bytes is checked.  The query needs no device.
  *   NDP_E_UNSUPPORTED: outside 1 <= K <= 32, 1 <= H <= 64, 1 <= cin, cout <= 1024, 1 <= nq, ns <= 2^30 on the large side.
  *   NDP_E_INVALID: a dimension < 1, a NULL or misaligned pointer, extent not positive and finite, influence outside 0..2,
@@ -434,6 +435,31 @@ int ndp_kpconv_forward_workspace(long long nq, long long ns, int H, int K, int c
 int ndp_kpconv_forward(const float *q, const float *s, const int *idx, const float *x, const float *W, const float *kp,
                        long long nq, long long ns, int H, int K, int cin, int cout, float extent, int influence, int aggregation,
                        int normalize, void *ws, long long ws_bytes, float *y, void *stream);
+/* KPConv backward (csrc/ndp_kpconv_bwd.inc; DESIGN.md "KPConv backward"), ABI 219: the gradient of sum(y * dy) of ndp_kpconv_forward in
+ * the features x and the weights W, for the same arguments and dy [nq][cout].
+ *     g[n,o] = dy[n,o] / count[n] (normalize 1, the forward's division; else dy)     dW[k,c,o] = sum_n wf[n,k,c] g[n,o]
+ *     dwf[n,k,c] = sum_o g[n,o] W[k,c,o]        dx[r,c] = sum over valid (n,h) with idx[n,h] == r of sum_k w(n,h,k) dwf[n,k,c]
+ *   count and the `closest` choice are constants; q, s and kp get no gradient.  w is recomputed from the points with the forward's
+ *   expressions; nothing of the forward is kept but its inputs.  dx [ns][cin] or dW [K][cin][cout] may be NULL: that gradient and its
+ *   launches are skipped (both NULL is refused).
+ *   fp32 on the f32-input MFMA, no atomics, one writer per output element per launch, every sum in one fixed order: the same bits run to
+ *   run.  dx[r,c] is ONE chain from +0 over the incoming edges of r in ascending (n,h): the library transposes the table by a stable
+ *   radix sort of the edge ids by support row (shadows -- every idx outside 0 .. ns-1 -- under a key no row reaches).  The per-edge
+ *   gradients pass through global memory in slabs of `slab_queries` queries, at most 64 MiB; a slab continues the chain its predecessor
+ *   left in dx, so the bits of dx do not depend on the slab size.  A support row without an incoming edge gets +0.  No [nq][K][cin]
+ *   array exists in global memory.  dW: a workgroup owns 16 x 16 x 64 of (k, c, o) and walks the query tiles in ascending order; where
+ *   that gives few workgroups the walk is cut into segments (a function of the dimensions only) whose partials one writer adds in
+ *   ascending order.  The bits of dW do not depend on slab_queries or on whether dx is asked for, and the other way round.
+ *   slab_queries: 0 (the library's choice: as many as 64 MiB hold) or a multiple of 16 whose slab fits 64 MiB.
+ *   ws: ndp_kpconv_backward_workspace(...) bytes for the same slab_queries, 16-byte aligned: the slab buffer and O(nq H + ns) integers
+ *   (flags, counts, the sort's keys, values and temporary storage, the row starts).  The query needs no device.  The edge count is
+ *   known on the host: ndp_kpconv_backward launches on `stream` and DOES NOT synchronise.  Every refusal precedes the first launch.
+ *   Refused as ndp_kpconv_forward, and NDP_E_INVALID: a NULL or misaligned dy, dx and dW both NULL, slab_queries negative, no multiple
+ *   of 16 or too large for 64 MiB; NDP_E_UNSUPPORTED: nq H >= 2^31 (an edge id is an int).                                         */
+int ndp_kpconv_backward_workspace(long long nq, long long ns, int H, int K, int cin, int cout, long long slab_queries, long long *nbytes);
+int ndp_kpconv_backward(const float *q, const float *s, const int *idx, const float *x, const float *W, const float *kp, const float *dy,
+                        long long nq, long long ns, int H, int K, int cin, int cout, float extent, int influence, int aggregation,
+                        int normalize, long long slab_queries, void *ws, long long ws_bytes, float *dx, float *dW, void *stream);
 
 /* Attention and the dense confidence matrix (csrc/ndp_attention.inc, the end of csrc/ndp_match.inc; DESIGN.md "Attention"), ABI 215:
  * what Lepard's repositioning transformer (correspondence/lepard/transformer.py, matching.py) needs between the KPFCN descriptors

@@ -49,6 +49,22 @@ def _rotation(d, o):
         My = m3([[c[:, 1], z, s[:, 1]], [z, one, z], [-s[:, 1], z, c[:, 1]]])
         Mz = m3([[c[:, 2], -s[:, 2], z], [s[:, 2], c[:, 2], z], [z, z, one]])
         return Mx @ My @ Mz
+    if d.rotfmt == "quaternion":                       # nets.py:154-157, rigid_body.py:58-85
+        raw = o[:, :4]
+        norm = raw.norm(dim=-1, keepdim=True)
+        q = raw / torch.where(raw[:, :1] < 0, -norm, norm)      # unit length, real part >= 0 (the norm carries component 0's sign)
+        w, x, y, z = q.unbind(-1)
+        k = 2.0 / (q * q).sum(-1)                      # 2 / |q|^2 of the normalised quaternion, as the reference forms it again
+        rows = [[1 - k * (y * y + z * z), k * (x * y - z * w), k * (x * z + y * w)],
+                [k * (x * y + z * w), 1 - k * (x * x + z * z), k * (y * z - x * w)],
+                [k * (x * z - y * w), k * (y * z + x * w), 1 - k * (x * x + y * y)]]
+        return torch.stack([torch.stack(q3, -1) for q3 in rows], -2)
+    if d.rotfmt == "6D":                               # rigid_body.py:5-16: Gram-Schmidt, rows b1, b2, b1 x b2
+        a1, a2 = o[:, 0:3], o[:, 3:6]
+        unit = lambda v: v / v.norm(dim=-1, keepdim=True).clamp_min(1e-12)         # (F.normalize's own floor)
+        b1 = unit(a1)
+        b2 = unit(a2 - (b1 * a2).sum(-1, keepdim=True) * b1)
+        return torch.stack([b1, b2, torch.linalg.cross(b1, b2, dim=-1)], -2)
     raise NotImplementedError(d.rotfmt)
 
 

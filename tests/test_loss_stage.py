@@ -10,6 +10,10 @@ tests/_loss_ref.py evaluated on the snapshot:
   nothing of another slot's dO touched;      (c) gmax bit-equal to max |dO| of what was written;      (d) the loss;      (e) every
   field of the next pair state against registration.py:226-249 restated in Python.
 
+Head layouts: the reference restates all four rotation formats (axis-angle, Euler, quaternion, 6D) under SE3 and Sim3, scene flow, and
+the nonrigidity gate behind any of them; test_head_variants and test_gated_engine run every layout of tests/_tick_ref.py's table, 3 to 11
+head rows.  Every other case runs se3aa.
+
 The bar has no constant: the SAME reference evaluated in float32 on the CPU is the yardstick of each case and tensor; the kernel's max
 error must stay within 4 yardsticks (floor 2^-22 max|ref|: a float32 run can happen to be exact).  No point is excluded anywhere.
 Measured figures of every case: build/reports/loss_stage_errors.json and .txt (untracked; a copy of the table is kept as
@@ -27,6 +31,7 @@ import torch
 
 from deformationpyramid_amd._native import DEC_ADVANCE, DEC_IDLE, DEC_STEP, DEC_STEP_ADVANCE          # (loads no library)
 from tests import _loss_ref as R
+from tests import _tick_ref as TR
 from tests._helpers import VARIANTS, engine_modes, scale_heads, seeded_pyramid
 
 pytestmark = pytest.mark.gpu
@@ -66,7 +71,10 @@ def _write_report():
 
 # ------------------------------------------------------------------------------------------------ the harness
 def _pyramid(variant, gated, m, seed):
-    pyr = seeded_pyramid(seed, m=m, nonrigidity_est=True, **VARIANTS[variant]) if gated else seeded_pyramid(seed, m=m, **VARIANTS[variant])
+    """variant: a tag of VARIANTS, or one of the layout table's (tests/_tick_ref.py: LAYOUTS) that VARIANTS does not have; the gate comes
+    from `gated` alone."""
+    kw = VARIANTS[variant] if variant in VARIANTS else {k: v for k, v in TR.LAYOUTS[variant].items() if k != "nonrigidity_est"}
+    pyr = seeded_pyramid(seed, m=m, nonrigidity_est=True, **kw) if gated else seeded_pyramid(seed, m=m, **kw)
     for lvl in range(m):
         scale_heads(pyr, lvl, HEAD_SCALE)
     return pyr
@@ -279,21 +287,44 @@ def test_truncation_below_every_distance_leaves_the_landmarks_alone(dev):
     assert abs(s.r64.loss - float(((s.r64.xw[:70] - lt) ** 2).sum(-1).mean())) == 0
 
 
-@pytest.mark.parametrize("variant", ["sim3eu", "sflow"])
+def _assert_margins(s, d):
+    """The quaternion and 6D heads of the case are far from their clamps (1e-12 in the kernel) and from 0 / 0; no axis-angle rotation
+    vector is near theta = 0 -- on the head outputs the forward kernel wrote (tests/test_tick_layouts_cpu.py: the same on the CPU)."""
+    mg = TR.rotation_margins(d, s.snap.heads[:s.n, :s.nh])
+    for k, v in mg.items():
+        assert v >= (1e-6 if k == "aa_norm" else 5e-4), (k, v)
+
+
+@pytest.mark.parametrize("variant", ["sim3eu", "sflow"] + [t for t in TR.UNGATED if t not in ("sim3eu", "sflow")])
 def test_head_variants(dev, variant):
+    """Every ungated layout of the table, 3 to 10 head rows: the row offsets of head_warp_bwd (scale, translation) behind 3, 4 and 6
+    rotation rows, and the 6D backward, which reads the raw rotation outputs out of the row it then overwrites with their gradient."""
     s = run_stage(dev, f"variant/{variant}", {0: (40, 300, 333)}, variant=variant, eng_kw=dict(gemm_mode=0, **LAT))[0]
-    assert s.nh == {"sim3eu": 7, "sflow": 3}[variant]
+    assert s.nh == TR.HEAD_ROWS[variant][0]
+    d = R.level_desc(s.snap.desc, 0)
+    _assert_margins(s, d)
+    for j in range(s.nh):                                        # no row of the layout is without a gradient
+        assert float(s.r64.dO[:, j].abs().max()) > 0, (variant, j)
 
 
-@pytest.mark.parametrize("level", [1, 0])
-def test_gated_engine(dev, level):
-    """se3aa with the nonrigidity gate, w_reg > 0: level 1 carries the BCE value and g_nr, level 0 of the same engine carries no gate."""
-    s = run_stage(dev, f"gated/level{level}", {0: (40, 300, 333)}, gated=True, level=level, m=2, cfg=dict(w_reg=0.5, iters=1),
-                  eng_kw=dict(gemm_mode=0, **LAT))[0]
-    assert s.eng.c_engine.w_reg == 0.5 and s.nh == (7 if level else 6)
+@pytest.mark.parametrize("tag,level", [pytest.param("se3aa", 1, id="1"), pytest.param("se3aa", 0, id="0")]
+                         + [pytest.param(t, lvl, id=f"{t}-{lvl}") for t in TR.GATED for lvl in (1, 0)])
+def test_gated_engine(dev, tag, level):
+    """A layout with the nonrigidity gate, w_reg > 0: level 1 carries the BCE value and g_nr, level 0 of the same engine carries no gate
+    -- the shorter layout next to a parameter block sized for the longer one.  se3aa (7 | 6 head rows) and the table's gated layouts:
+    the gate row behind a lone translation (4 | 3), behind a quaternion (8 | 7), and behind 6D rows, a Sim3 scale row and the
+    translation (11 | 10)."""
+    variant = tag[:-3] if tag.endswith("_nr") else tag
+    s = run_stage(dev, f"gated/level{level}" if tag == "se3aa" else f"gated/{tag}/level{level}", {0: (40, 300, 333)}, variant=variant,
+                  gated=True, level=level, m=2, cfg=dict(w_reg=0.5, iters=1), eng_kw=dict(gemm_mode=0, **LAT))[0]
+    d = R.level_desc(s.snap.desc, level)
+    rows = (6, 7) if tag == "se3aa" else TR.HEAD_ROWS[tag]
+    assert s.snap.desc.nonrigidity and s.eng.c_engine.w_reg == 0.5 and s.nh == rows[1 if level else 0] == d.n_heads
+    _assert_margins(s, d)
     plain = R.evaluate(SimpleNamespace(**dict(vars(s.snap), w_reg=0.0)))
     if level:
-        assert s.r64.loss - plain.loss > 0.1 and s.dO[:340, 6].abs().max() > 0          # ~ 0.5 * log 2, and a gradient on the gate row
+        assert d.row_nr == s.nh - 1
+        assert s.r64.loss - plain.loss > 0.1 and s.dO[:340, d.row_nr].abs().max() > 0    # ~ 0.5 * log 2, and a gradient on the gate row
     else:
         assert s.r64.loss == plain.loss and s.st.cur == 0
     assert s.nst.decision == DEC_STEP_ADVANCE

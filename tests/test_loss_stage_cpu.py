@@ -10,6 +10,7 @@ import torch
 
 from deformationpyramid_amd.layout import LayerDesc
 from tests import _loss_ref as R
+from tests import _tick_ref as TR
 
 BAR = 2e-6                       # test_chamfer_loss_and_grad's, relative to the loss / to max |grad|
 
@@ -63,22 +64,60 @@ def test_reference_with_landmarks_is_landmark_plus_w_cd_chamfer(trunc):
     assert np.abs(ref.gx.numpy()[K:] - w_cd * r["gx"]).max() < BAR * np.abs(w_cd * r["gx"]).max()
 
 
+def _layout_desc(tag):
+    """The descriptor of a level that carries every row of the layout (a gated layout: a level >= 1)."""
+    kw = TR.LAYOUTS[tag]
+    return LayerDesc(motion=kw["motion"], rotfmt=kw["rotation_format"], nonrigidity=bool(kw.get("nonrigidity_est", False)))
+
+
 def test_reference_head_backward_is_the_chain_rule_of_its_own_warp():
-    """dO = mlp_scale J^T gx for the three head families the GPU cases use (finite differences of head_warp in float64)."""
-    for motion, rotfmt, nonrig in (("SE3", "axis_angle", False), ("Sim3", "euler", False), ("sflow", "axis_angle", False),
-                                   ("SE3", "axis_angle", True)):
-        d = LayerDesc(motion=motion, rotfmt=rotfmt, nonrigidity=nonrig)
+    """dO = mlp_scale J^T gx for every head layout the GPU cases use (finite differences of head_warp in float64), at head outputs of
+    the size those cases see (5e-3).  The quaternion and 6D heads divide by norms of that size, so the warp's higher derivatives grow
+    like norm^-k: the differences are the five-point stencil (error h^4 f^(5) / 30) at h = 3e-7 -- at 1e-6 the three-point stencil's
+    own h^2 f''' / 6 is 1e-6 for these heads, a hundred times the bar."""
+    for tag in TR.LAYOUTS:
+        d = _layout_desc(tag)
+        assert d.n_heads == TR.HEAD_ROWS[tag][1]
         g = torch.Generator().manual_seed(5)
-        o = ((torch.rand(6, d.n_heads, generator=g) - 0.5) * 0.04).double()
+        o = ((torch.rand(6, d.n_heads, generator=g) - 0.5) * 0.01).double()
         x = R.cloud(6, 9).double()
         gx = torch.rand(6, 3, generator=g).double()
+        mg = TR.rotation_margins(d, o)
+        assert all(v > 1.5e-3 for v in mg.values()), mg             # the stencil's error estimate above rests on it
         oo = o.clone().requires_grad_()
         (R.head_warp(d, oo, x)[0] * gx).sum().backward()
+        f = lambda q: (R.head_warp(d, q, x)[0] * gx).sum(-1)
+        h = 3e-7
         for j in range(d.n_heads):
             e = torch.zeros_like(o)
-            e[:, j] = 1e-6
-            fd = ((R.head_warp(d, o + e, x)[0] - R.head_warp(d, o - e, x)[0]) * gx).sum(-1) / 2e-6
-            assert (fd - oo.grad[:, j]).abs().max() < 1e-8, (motion, rotfmt, nonrig, j)
+            e[:, j] = h
+            fd = (-f(o + 2 * e) + 8 * f(o + e) - 8 * f(o - e) + f(o - 2 * e)) / (12 * h)
+            assert (fd - oo.grad[:, j]).abs().max() < 1e-8, (tag, j, float((fd - oo.grad[:, j]).abs().max()))
+            assert float(oo.grad[:, j].abs().max()) > 1e-3, (tag, j)              # every row of the layout moves the warp
+
+
+@pytest.mark.parametrize("tag", list(TR.LAYOUTS))
+def test_restated_warp_is_the_oracles_level_forward(tag):
+    """head_warp on float64 head outputs (MLP + mlp_scale from the level's parameters) against the CPU oracle's level forward -- which is
+    pinned to the reference's own outputs by fixtures F2 / F11 -- at test_level_fwd_matches_oracle's tolerances.  Levels 0, 1, 2 of a
+    pyramid with the heads x 20: a gated layout's level 0 has no gate row."""
+    pyr = TR.tick_pyramid(tag, 3)
+    x = R.cloud(200, 17)
+    tol = 1e-5 if ("6d" in tag or "quat" in tag) else 2e-6
+    for level in (0, 1, 2):
+        d = R.level_desc(pyr.descs[-1], level)
+        assert d == pyr.descs[level]
+        params = pyr.store[level, :d.param_count]
+        xw, nr = R.head_warp(d, TR.level_heads(d, params, level, x), x.double())
+        cd = O().make_desc(d.width, d.n_hidden, d.motion, d.rotfmt, d.nonrigidity, d.mlp_scale)
+        ref, ref_nr = O().level_fwd(cd, params.numpy(), level, TR.K0, x.numpy(), want_nonrig=True)
+        err = float(np.abs(xw.numpy() - ref).max())
+        print(f"{tag} level {level}: |restated warp - oracle| = {err:.3e}, largest displacement {float((xw - x.double()).abs().max()):.3e}")
+        assert err < tol, (tag, level, err)
+        assert float((xw - x.double()).abs().max()) > 5e-4             # a warp that moves the points, not the identity
+        assert (nr is not None) == (tag in TR.GATED and level > 0)
+        if nr is not None:
+            assert float(np.abs(nr.numpy() - ref_nr).max()) < 2e-6, (tag, level)
 
 
 def test_crafted_indices_stay_inside_their_range():

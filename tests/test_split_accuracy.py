@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests._helpers import VARIANTS, seeded_pyramid, scale_heads
+from tests._tick_ref import _errors, _f64_reference, _kernel_outputs, _run_tick_by_stages       # (moved there: tests/test_tick_layouts.py shares them)
 
 pytestmark = pytest.mark.gpu
 K0 = -8
@@ -25,139 +26,6 @@ def dev():
     from deformationpyramid_amd import _native
     _native.lib()
     return torch.device("cuda:0")
-
-
-def _run_tick_by_stages(dev, tag, gemm_mode, S, T, level, head_scale, G=None, w_cd=1.0, tiny_h0=False, b1=None, keep_h0=True):  # noqa: C901
-    """One tick of a one-pair engine at `level`, stage by stage; returns every buffer a kernel consumed or produced (CPU, fp32).
-    w_cd: weight of the loss (every gradient scales with it).  tiny_h0: layer 0 of the level = (W0 = 0, b0 = 1e-9), i.e. every
-    h0 is positive and below fp16's smallest subnormal (and h1 = relu(1e-9 W1 1 + b1) has such elements too)."""
-    from deformationpyramid_amd.engine import BatchedEngine, OptConfig
-    m = level + 1
-    pyr = seeded_pyramid(11, m=m, **VARIANTS[tag])
-    for lvl in range(m):
-        scale_heads(pyr, lvl, head_scale)                   # head outputs of O(0.01): rotations / translations that matter
-    d = pyr.descs[0]
-    if tiny_h0:
-        with torch.no_grad():
-            pyr.store[level, d.off_W(0):d.off_W(0) + d.width * 6] = 0.0
-            pyr.store[level, d.off_b(0):d.off_b(0) + d.width] = 1e-9
-            pyr.store[level, d.off_b(1):d.off_b(1) + d.width] = 0.0
-    if b1 is not None:
-        with torch.no_grad():
-            pyr.store[level, d.off_b(1):d.off_b(1) + d.width] = b1
-    cfg = OptConfig(m=m, iters=2, early_stop=False, w_cd=w_cd)
-    # gemm_mode 7: the split forward does not store h0 (bwd1 recomputes it); bit 8 makes it store h0 for the comparisons below --
-    # test_h0_is_recomputed... pins that the bit changes nothing else
-    # + 32: the fused backward (one launch for both layers, dz1 in LDS) also writes dz1 to HBM, where the two-launch form leaves it
-    # + 1024: the whole Adam step in the update stage -- at G = 1 the default steps the two 128 x 128 matrices behind the fused backward's
-    # tile loop and writes no partial of them (bitwise the same state: test_adam_behind_the_backward_is_bitwise_the_update_stage)
-    mode = gemm_mode if (gemm_mode & 7) != 7 else (gemm_mode | 1024 | (0 if gemm_mode & 16 else 32) | (8 if keep_h0 else 0))
-    eng = BatchedEngine(d, cfg, 1, n_cap=S, t_cap=T, device=dev, gemm_mode=mode, nn_mode=1, G=G)
-    g = torch.Generator().manual_seed(3)
-    src = (torch.rand(S, 3, generator=g) - 0.5).contiguous()
-    tgt = ((torch.rand(T, 3, generator=g) - 0.5) * 1.05 + 0.02).contiguous()
-    eng.load(0, src, 0, S, None, tgt, pyr.store)
-    for _ in range(2 * level):                               # iters = 2 per level: arrive at `level` with trained lower levels
-        eng.run_ticks(1)
-    st = eng.read_states()[0]
-    assert st.level == level
-    P = d.param_count
-    out = {"desc": d, "n": S, "params": eng.params[0, level, :P].cpu().clone()}
-    eng.act.fill_(float("nan"))                           # whatever a kernel does not write must not look like data
-    eng.run_stages(0, 2)                                      # forward, nearest neighbours, loss / dL/dx'
-    torch.cuda.synchronize()
-    out["act_fwd"] = eng.act[0].cpu().clone()                 # h0, h1, h2
-    if (mode & 7) == 7 and not mode & 16:                     # the fused backward reads h1 and (round 6) h2 as the forward's plane images, not as fp32 rows
-        out["act_fwd"][1] = _decode_plane_image(out["act_fwd"][1])
-        out["act_fwd"][2] = _decode_plane_image(out["act_fwd"][2])
-    out["heads"] = eng.heads[0].cpu().clone()
-    out["dO"] = eng.dO[0].cpu().clone()
-    eng.run_stages(3, 3)                                      # bwd2
-    torch.cuda.synchronize()
-    out["dz1"] = eng.act[0, 2].cpu().clone()
-    out["g_bwd2"] = eng.gpart[0].double().sum(0)[:P].cpu().clone()
-    eng.run_stages(4, 4)                                      # bwd1
-    torch.cuda.synchronize()
-    out["g_all"] = eng.gpart[0].double().sum(0)[:P].cpu().clone()
-    eng.run_stages(5, 5)
-    torch.cuda.synchronize()
-    return out
-
-
-def _decode_plane_image(act1):
-    """A plane image (h1; since round 6 also h2) the split forward leaves for the FUSED backward (gemm_mode 7): per 64-point tile 32 KB -- the footprint of the
-    fp32 rows it replaces -- holding two fp16 planes [64][128], hi = fp16(2^6 h1) and lo = fp16(2^6 h1 - hi), each row's sixteen
-    16-byte granules XOR-swizzled (ndp_fwd_split.inc: bf_swz).  -> [rows][128] float32 (hi + lo carries 22 bits: exact in fp32)."""
-    rows = act1.shape[0] // 64 * 64
-    img = act1[:rows].contiguous().view(torch.float16).view(rows // 64, 2, 64, 128).float()
-    p = torch.arange(64)
-    g = torch.tensor([0, 2, 3, 1])
-    swz = ((((p & 3) << 2) | g[(p >> 2) & 3]) << 3)[:, None]
-    idx = (torch.arange(128)[None, :] ^ swz).expand(rows // 64, 2, 64, 128)
-    planes = torch.gather(img, 3, idx)
-    out = torch.full_like(act1, float("nan"))
-    val = (planes[:, 0] + planes[:, 1]) / 64.0
-    # the ReLU mask is the HI plane's SIGN BIT (round 6: hi = -0 where the pre-activation is <= 0, hi >= +0 where it is positive -- a
-    # positive activation below fp16's range has hi = +0 and its value in lo, or nothing at all): a positive element whose parts sum to
-    # zero decodes to a positive value below everything else
-    val = torch.where(~torch.signbit(planes[:, 0]) & (val <= 0), torch.full_like(val, 2.0 ** -40), val)
-    out[:rows] = val.reshape(rows, 128)
-    return out
-
-
-def _f64_reference(r):
-    """float64 evaluation of each kernel from that kernel's own inputs."""
-    d, n, P = r["desc"], r["n"], r["params"].double()
-    W = d.width
-    nh = d.n_heads
-    W0 = P[d.off_W(0):d.off_W(0) + W * 6].view(W, 6); b0 = P[d.off_b(0):d.off_b(0) + W]
-    W1 = P[d.off_W(1):d.off_W(1) + W * W].view(W, W); b1 = P[d.off_b(1):d.off_b(1) + W]
-    W2 = P[d.off_W(2):d.off_W(2) + W * W].view(W, W); b2 = P[d.off_b(2):d.off_b(2) + W]
-    Wh = P[d.off_Wh:d.off_Wh + nh * W].view(nh, W); bh = P[d.off_bh:d.off_bh + nh]
-    pe = r["heads"][:n, 16:22].double()                       # the forward's own layer-0 input
-    ref = {}
-    # ---- forward: pe -> h0, h1, h2, scaled head outputs
-    h0 = torch.relu(pe @ W0.T + b0); h1 = torch.relu(h0 @ W1.T + b1); h2 = torch.relu(h1 @ W2.T + b2)
-    ref["h0"], ref["h1"], ref["h2"] = h0, h1, h2
-    ref["heads"] = d.mlp_scale * (h2 @ Wh.T + bh)
-    # ---- bwd2 from ITS inputs: dO, h2, h1 as the forward kernel left them
-    dO = r["dO"][:n, :nh].double()
-    g_h0, g_h1, g_h2 = (r["act_fwd"][k, :n].double() for k in range(3))
-    dz2 = (dO @ Wh) * (g_h2 > 0)
-    ref["dWh"], ref["dbh"] = dO.T @ g_h2, dO.sum(0)
-    ref["dW2"], ref["db2"] = dz2.T @ g_h1, dz2.sum(0)
-    ref["dz1"] = (dz2 @ W2) * (g_h1 > 0)
-    # ---- bwd1 from ITS inputs: dz1 as bwd2 left it, h0, pe
-    dz1 = r["dz1"][:n].double()
-    ref["dW1"], ref["db1"] = dz1.T @ g_h0, dz1.sum(0)
-    dz0 = (dz1 @ W1) * (g_h0 > 0)
-    ref["dW0"], ref["db0"] = dz0.T @ pe, dz0.sum(0)
-    return ref
-
-
-def _kernel_outputs(r):
-    d, n, W, nh = r["desc"], r["n"], r["desc"].width, r["desc"].n_heads
-    ga, g2 = r["g_all"], r["g_bwd2"]
-    return {
-        "h0": r["act_fwd"][0, :n].double(), "h1": r["act_fwd"][1, :n].double(), "h2": r["act_fwd"][2, :n].double(),
-        "heads": r["heads"][:n, :nh].double(),
-        "dWh": g2[d.off_Wh:d.off_Wh + nh * W].view(nh, W), "dbh": g2[d.off_bh:d.off_bh + nh],
-        "dW2": g2[d.off_W(2):d.off_W(2) + W * W].view(W, W), "db2": g2[d.off_b(2):d.off_b(2) + W],
-        "dz1": r["dz1"][:n].double(),
-        "dW1": ga[d.off_W(1):d.off_W(1) + W * W].view(W, W), "db1": ga[d.off_b(1):d.off_b(1) + W],
-        "dW0": ga[d.off_W(0):d.off_W(0) + W * 6].view(W, 6), "db0": ga[d.off_b(0):d.off_b(0) + W],
-    }
-
-
-def _errors(r):
-    """per tensor: (max |error| / max |reference|, rms error / rms reference, number of elements)."""
-    ref, got = _f64_reference(r), _kernel_outputs(r)
-    out = {}
-    for k in ref:
-        e = got[k] - ref[k]
-        out[k] = (float(e.abs().max() / ref[k].abs().max().clamp_min(1e-300)),
-                  float(e.pow(2).mean().sqrt() / ref[k].pow(2).mean().sqrt().clamp_min(1e-300)), ref[k].numel())
-    return out
 
 
 @pytest.mark.parametrize("G", [None, 2, 1])
